@@ -14,6 +14,17 @@ Weights are random-init (no checkpoints offline) with the exact Llama-3-8B
 architecture; prompts are synthetic English.
 
 python bench.py [--gpus N] [--steps K] [--warmup W] [--sessions 50] [--gen 128]
+                [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the ``--steps`` turns and prints the JSON
+line; nothing else is measured.  Every session samples with a fixed seed derived
+from ``--seed``, its rank and its index, so the prompts and the sampling streams
+are identical from run to run.  ``--dump-outputs DIR`` also writes what the
+sessions received in the last timed turn (``DIR/reply_text.npy``: one row of
+Unicode code points per session, padded with -1 to ``8 * gen`` columns;
+``DIR/reply_tokens.npy``: tokens generated per session; both float32).  ``--full``
+is where further measurements (anything beyond the headline figure) belong; there
+are none today, so it runs the same turns.
 
 ``--gpus N`` with N > 1 and no ``WORLD_SIZE`` in the environment: this process
 becomes a launcher that starts N rank processes itself (``RANK`` / ``LOCAL_RANK``
@@ -71,6 +82,32 @@ def _heartbeat(state: dict, period: float = 30.0):
                       flush=True)
 
     threading.Thread(target=run, daemon=True, name="bench-heartbeat").start()
+
+
+DUMP_BUDGET = 60 << 20   # bytes of .npy payload --dump-outputs may write
+
+
+def _dump_outputs(path: str, texts, tokens, gen: int) -> None:
+    """Write the last timed turn's replies as float32 arrays: ``reply_text.npy`` [sessions,
+    8 * gen] (code points of each session's reply in rank-major session order, -1 padded,
+    longer replies cut) and ``reply_tokens.npy`` [sessions].  Past the size budget a fixed,
+    seeded sample of the sessions is kept (its indices in ``reply_rows.npy``)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    width = 8 * max(1, gen)
+    rows = np.arange(len(texts))
+    max_rows = max(1, DUMP_BUDGET // (4 * (width + 2)))
+    if len(rows) > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(len(texts), max_rows, replace=False))
+    arr = np.full((len(rows), width), -1.0, np.float32)
+    for i, r in enumerate(rows):
+        cp = [ord(c) for c in texts[r][:width]]
+        arr[i, :len(cp)] = cp
+    np.save(os.path.join(path, "reply_text.npy"), arr)
+    np.save(os.path.join(path, "reply_tokens.npy"), np.asarray([tokens[r] for r in rows], np.float32))
+    if len(rows) < len(texts):
+        np.save(os.path.join(path, "reply_rows.npy"), rows.astype(np.float32))
 
 
 def _launch_ranks(n: int, argv) -> int:
@@ -178,7 +215,17 @@ def main():
     ap.add_argument("--agent-tools", type=float, default=-1.0, metavar="FRAC",
                     help="BASELINE config 5: agent with JSON-guided tool calls, FRAC of the turns "
                          "ask for a web search (stub backend); e.g. 0.2")
+    ap.add_argument("--seed", type=int, default=0,
+                    help="base of the sessions' sampling seeds (each session: seed, rank and index)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed turns write what every session received in the last one "
+                         "as DIR/reply_text.npy and DIR/reply_tokens.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none today: the "
+                         "other configurations are selected by their own options)")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("bench: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ:
         if (a.gpus or 1) > 1:
             sys.exit(_launch_ranks(a.gpus, sys.argv[1:]))
@@ -215,7 +262,7 @@ def main():
     sess_cfg = {"system_prompt": "You are a helpful voice assistant. Keep responses concise and "
                                  "conversational.",
                 "temperature": a.temperature, "top_p": a.top_p, "max_tokens": a.gen,
-                "ignore_eos": True}
+                "ignore_eos": True, "seed": a.seed}
     ctx = mp.get_context("spawn")
     parent_conn, child_conn = ctx.Pipe()
     client = ctx.Process(target=client_process, daemon=True,
@@ -366,6 +413,8 @@ def main():
         if not cpu:
             torch.cuda.synchronize()
 
+    if a.dump_outputs:
+        cmd(("keep_text", True))
     barrier()
     m_before = engine.engine.metrics()
     t0 = time.perf_counter()
@@ -396,6 +445,7 @@ def main():
     summ = summarize(res)
     local = {"tokens": res["tokens"], "frames": res.get("frames", 0), "elapsed": elapsed,
              "placed": placed,
+             "last_texts": res.get("last_texts"), "last_tokens": res.get("last_tokens"),
              "ttft": res["ttft_s"], "tool_ttft": res.get("tool_ttft_s", []),
              "server_ttft": res.get("server_ttft_ms", []),
              "engine_ttft": res.get("engine_ttft_ms", []),
@@ -416,6 +466,9 @@ def main():
     ctx = _timed_ctx(m_before, metrics)
     mlabel = _model_label(a.model)
     if rank == 0:
+        if a.dump_outputs:
+            _dump_outputs(a.dump_outputs, [t for r in allr for t in r["last_texts"]],
+                          [n for r in allr for n in r["last_tokens"]], a.gen)
         out = {
             "metric": f"output tokens/sec (node) + p50 TTFT over WebSocket, {mlabel} at "
                       f"{a.sessions} session{'s' if a.sessions != 1 else ''}"
@@ -552,7 +605,7 @@ def bench_tp(a, rank: int, world: int, local_rank: int):
     sess_cfg = {"system_prompt": "You are a helpful voice assistant. Keep responses concise and "
                                  "conversational.",
                 "temperature": a.temperature, "top_p": a.top_p, "max_tokens": a.gen,
-                "ignore_eos": True}
+                "ignore_eos": True, "seed": a.seed}
     client = parent_conn = None
     if rank == 0:
         ctx = mp.get_context("spawn")
@@ -638,6 +691,8 @@ def bench_tp(a, rank: int, world: int, local_rank: int):
     hb["phase"] = "warmup turns"
     if a.warmup > 0:
         cmd(("run", a.warmup))
+    if a.dump_outputs:
+        cmd(("keep_text", True))
     sync()
     hb["phase"] = "timed turns"
     m0 = eng.metrics()
@@ -662,6 +717,8 @@ def bench_tp(a, rank: int, world: int, local_rank: int):
     metrics = eng.metrics()
     ctx = _timed_ctx(m0, metrics)
     value = res["tokens"] / elapsed
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, res["last_texts"], res["last_tokens"], a.gen)
     out = {
         "metric": "output tokens/sec (node) + p50 TTFT over WebSocket, "
                   f"{a.model} TP={world} at {a.sessions} sessions",

@@ -53,17 +53,25 @@ class Session:
         self.url = url
         self.cfg = cfg
         self.words = words
-        self.rng = random.Random(seed * 7919 + idx)
+        self.stream = seed * 7919 + idx
+        self.rng = random.Random(self.stream)
         self.ws = None
         self.http = None
         self.turns: List[Dict[str, Any]] = []
+        self.keep_text = False      # LoadClient.keep_text: remember the last turn's reply
+        self.last_text = ""
 
     async def open(self, http):
         self.http = http
         self.ws = await http.ws_connect(self.url, max_msg_size=0, heartbeat=None)
         m = await self.ws.receive_json()
         assert m["type"] == "session_started", m
-        await self.ws.send_json({"type": "start_session", "config": self.cfg})
+        cfg = self.cfg
+        if cfg.get("seed") is not None:
+            # a run-to-run identical sampling stream per session (the engine draws a random
+            # seed for a request that brings none)
+            cfg = dict(cfg, seed=int(cfg["seed"]) * 1000003 + self.stream)
+        await self.ws.send_json({"type": "start_session", "config": cfg})
         m = await self.ws.receive_json()
         assert m["type"] == "session_configured", m
 
@@ -73,6 +81,7 @@ class Session:
         await self.ws.send_json({"type": "user_message", "text": text})
         first = None
         frames = 0
+        parts: Optional[List[str]] = [] if self.keep_text else None
         while True:
             msg = await self.ws.receive()
             m = json.loads(msg.data)
@@ -81,7 +90,11 @@ class Session:
                 frames += 1
                 if first is None:
                     first = time.perf_counter() - t0
+                if parts is not None:
+                    parts.append(m.get("data") or "")
             elif t == "response_complete":
+                if parts is not None:
+                    self.last_text = "".join(parts)
                 st = m["stats"]
                 rec = {"ttft_s": first if first is not None else time.perf_counter() - t0,
                        "latency_s": time.perf_counter() - t0, "frames": frames,
@@ -118,6 +131,7 @@ class LoadClient:
         self.seed = seed
         self.sessions: List[Session] = []
         self.http = None
+        self.keep_text = False      # run_turns() also returns every session's last reply
 
     async def open(self):
         import aiohttp
@@ -133,6 +147,7 @@ class LoadClient:
 
         async def one(s: Session):
             out = []
+            s.keep_text = self.keep_text
             for _ in range(turns):
                 out.append(await s.turn())
             return out
@@ -147,7 +162,10 @@ class LoadClient:
                 "server_ttft_ms": [r["server_ttft_ms"] for r in recs if r["server_ttft_ms"] is not None],
                 "engine_ttft_ms": [r["engine_ttft_ms"] for r in recs if r["engine_ttft_ms"] is not None],
                 "cached_prompt_tokens": sum(r["cached_prompt_tokens"] or 0 for r in recs),
-                "prompt_tokens": sum(r["prompt_tokens"] or 0 for r in recs), "turns": len(recs)}
+                "prompt_tokens": sum(r["prompt_tokens"] or 0 for r in recs), "turns": len(recs),
+                # what each session received in its last turn, in session order
+                "last_texts": [s.last_text for s in self.sessions] if self.keep_text else None,
+                "last_tokens": [rs[-1]["tokens"] if rs else 0 for rs in res]}
 
     async def close(self):
         await asyncio.gather(*[s.close() for s in self.sessions], return_exceptions=True)
@@ -170,6 +188,9 @@ def client_process(conn, url: str, sessions: int, cfg: Dict[str, Any], words: in
                     conn.send({"ok": True})
                 elif isinstance(cmd, tuple) and cmd[0] == "url":   # before "open"
                     lc.url = cmd[1]
+                    conn.send({"ok": True})
+                elif isinstance(cmd, tuple) and cmd[0] == "keep_text":
+                    lc.keep_text = bool(cmd[1])
                     conn.send({"ok": True})
                 elif isinstance(cmd, tuple) and cmd[0] == "run":
                     conn.send({"ok": True, "result": loop.run_until_complete(lc.run_turns(cmd[1]))})

@@ -77,6 +77,29 @@ def test_eight_ranks_through_the_front_door():
     assert sorted(d["rank"] for d in out["rank_devices"]) == list(range(8))
 
 
+def test_dump_outputs_writes_the_last_turn_and_repeats(tmp_path):
+    """--dump-outputs DIR: the replies of the last timed turn as float32 .npy files, one
+    row per session; the sessions' seeds are fixed, so a second run with the same
+    arguments writes the same arrays.  --full is accepted and changes neither."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = _run(["--gpus", "1", "--device", "cpu", "--model", "tiny", "--sessions", "3", "--steps", "2",
+                  "--warmup", "1", "--gen", "6", "--words", "6", "--dump-outputs", str(d)] + extra)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = _json_lines(r.stdout)[0]
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        text, toks = np.load(d / "reply_text.npy"), np.load(d / "reply_tokens.npy")
+        assert sorted(p.name for p in d.iterdir()) == ["reply_text.npy", "reply_tokens.npy"]
+        assert text.dtype == np.float32 and text.shape == (3, 48)
+        assert toks.dtype == np.float32 and toks.tolist() == [6.0, 6.0, 6.0]
+        assert ((text >= 0).sum(axis=1) > 0).all() and (text >= -1).all()
+        dumps.append((text, toks))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
 def test_fp8_kv_cache_flag_reaches_the_engine_and_the_json():
     """--kv-cache-dtype fp8 sets ENGINE_KV_CACHE_DTYPE for the service the bench drives
     (one rank here), the run completes on the fp8 pool and the JSON line says so."""
