@@ -2,6 +2,7 @@
 sequences with ragged 1.5-4.5k contexts, GQA 4 (Llama-3-8B), cold caches (several
 KV copies alternate inside one hipGraph).  Prints us per call and the KV bytes
 streamed per second.  FT_DECODE_RING8 (read once per process) picks the fp8 ring.
+KV_SCALES=1 passes per-head K / V scales to the fp8 calls (default: none, scale 1.0).
 
 python bench/attn_fp8_bench.py
 """
@@ -18,6 +19,7 @@ from gemm_sweep import graph_time  # noqa: E402
 
 nq, nkv, d = 32, 8, 128
 bs = int(os.environ.get("BS", "16"))   # KV block size (tokens)
+SCALES = os.environ.get("KV_SCALES", "0") == "1"
 
 
 def main():
@@ -39,6 +41,8 @@ def main():
         cnt = ops.decode_counters(B, nkv, "cuda")
         out = torch.empty(B, nq * d, device="cuda").bfloat16()
         res = {}
+        h = torch.arange(nkv, dtype=torch.float32, device="cuda")
+        ks, vs = 0.37 * (h + 1), 2.0 ** (h % 4 - 1) * 1.1
         for name, dt in (("bf16", torch.bfloat16), ("fp8", torch.float8_e4m3fn)):
             ncopy = 3 if dt == torch.bfloat16 else 6
             kvs = []
@@ -46,8 +50,9 @@ def main():
                 k = torch.randn(total + 8, nkv, bs, d, device="cuda").to(dt)
                 v = torch.randn(total + 8, nkv, d, bs, device="cuda").to(dt)
                 kvs.append((k, v))
+            sc = dict(k_scale=ks, v_scale=vs) if SCALES and name == "fp8" else {}
             fns = [(lambda k=k, v=v: ops.decode_attention(out, q, k, v, bt, sl, tmp[0], tmp[1], nq, nkv, d,
-                                                          d ** -0.5, counters=cnt)) for k, v in kvs] * 4
+                                                          d ** -0.5, counters=cnt, **sc)) for k, v in kvs] * 4
             us = graph_time(fns)
             nbytes = sum(lens) * nkv * d * 2 * kvs[0][0].element_size()
             res[name] = us
@@ -55,7 +60,8 @@ def main():
             del kvs, fns
             torch.cuda.empty_cache()
         print(f"B={B} ctx {lo}-{hi}: fp8 / bf16 = {res['fp8'] / res['bf16']:.3f} "
-              f"(ring8 {os.environ.get('FT_DECODE_RING8', '2')}, wpc8 {os.environ.get('FT_DECODE_WPC8', '1')})", flush=True)
+              f"(ring8 {os.environ.get('FT_DECODE_RING8', '2')}, wpc8 {os.environ.get('FT_DECODE_WPC8', '1')}, "
+              f"kv scales {'per head' if SCALES else 'none'})", flush=True)
 
 
 if __name__ == "__main__":

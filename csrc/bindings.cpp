@@ -17,7 +17,7 @@ int ft_silu_mul(void* out, const void* gu, int rows, int inter, int il, hipStrea
 int ft_rope_kv_write(void* qkv, int qkv_stride, const int* positions, const float* cos_sin,
                      const int* slot_mapping, void* k_cache, void* v_cache, int tokens, int nq,
                      int nkv, int head_dim, int block_size, int cos_rows, int num_slots, int kv8,
-                     hipStream_t stream);
+                     const float* k_inv, const float* v_inv, hipStream_t stream);
 int ft_decode_waves();
 int ft_decode_max_batch();
 int ft_paged_decode_attention(void* out, int out_stride, float* tmp_out, float* tmp_ml,
@@ -25,7 +25,8 @@ int ft_paged_decode_attention(void* out, int out_stride, float* tmp_out, float* 
                               const void* v_cache, const int* block_tables, int bt_stride,
                               const int* seq_lens, int batch, int nq, int nkv, int head_dim,
                               int block_size, float scale, int* counters, int piece,
-                              int slot_cap, int num_blocks, int kv8, hipStream_t stream);
+                              int slot_cap, int num_blocks, int kv8, const float* k_scale,
+                              const float* v_scale, hipStream_t stream);
 int ft_prefill_tile_tokens(int nq, int nkv);
 int ft_prefill_attention(void* out, int out_stride, const void* q, int q_stride,
                          const void* k_cache, const void* v_cache, const int* block_tables,
@@ -33,7 +34,8 @@ int ft_prefill_attention(void* out, int out_stride, const void* q, int q_stride,
                          const int* tile_info, int num_tiles, int nq, int nkv, int head_dim,
                          int block_size, float scale, float* part_o, float* part_ml,
                          const int* combine, int num_combine, int invariant, int num_blocks,
-                         int kv8, hipStream_t stream);
+                         int kv8, const float* k_scale, const float* v_scale,
+                         hipStream_t stream);
 int ft_sample(int* out_tokens, const void* logits, int logits_is_bf16, long logit_stride,
               int batch, int vocab, const float* temperature, const float* top_p,
               const int* top_k, const long long* seeds, const int* steps,
@@ -102,7 +104,7 @@ int ft_slab_rope_kv(const float* ws, int splits, int rows, int cols, void* q_out
                     const int* positions, const float* cos_sin, const int* slot_mapping,
                     void* k_cache, void* v_cache, int nq, int nkv, int head_dim, int block_size,
                     const void* residual, int hidden, float eps, int cos_rows, int num_slots,
-                    int kv8, hipStream_t stream);
+                    int kv8, const float* k_inv, const float* v_inv, hipStream_t stream);
 }
 
 namespace {
@@ -150,6 +152,19 @@ bool check_kv_caches(const at::Tensor& k_cache, const at::Tensor& v_cache, int64
   return kv8;
 }
 
+// per-head fp8 KV scale (or reciprocal) tensor: fp32 [nkv], contiguous, on the caches'
+// device, and only with float8_e4m3fn caches; absent = 1.0 (nullptr)
+const float* kv_scale_ptr(const c10::optional<at::Tensor>& s, const at::Tensor& k_cache, bool kv8,
+                          int64_t nkv, const char* name) {
+  if (!s.has_value()) return nullptr;
+  TORCH_CHECK(kv8, name, ": KV scales are given only with float8_e4m3fn caches");
+  TORCH_CHECK(s->scalar_type() == at::kFloat, name, " must be float32");
+  TORCH_CHECK(s->is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(s->device() == k_cache.device(), name, " must be on the caches' device");
+  TORCH_CHECK(s->dim() == 1 && s->size(0) == nkv, name, " must have shape [nkv]");
+  return s->data_ptr<float>();
+}
+
 void rmsnorm(at::Tensor out, at::Tensor x, at::Tensor w, double eps) {
   check_bf16(out, "out");
   check_bf16(x, "x");
@@ -195,7 +210,8 @@ void silu_mul(at::Tensor out, at::Tensor gu, bool il) {
 
 void rope_kv_write(at::Tensor qkv, at::Tensor positions, at::Tensor cos_sin,
                    at::Tensor slot_mapping, at::Tensor k_cache, at::Tensor v_cache, int64_t nq,
-                   int64_t nkv, int64_t head_dim) {
+                   int64_t nkv, int64_t head_dim, c10::optional<at::Tensor> k_inv,
+                   c10::optional<at::Tensor> v_inv) {
   check_bf16(qkv, "qkv");
   check_rows(qkv, "qkv");
   check_i32(positions, "positions");
@@ -205,6 +221,8 @@ void rope_kv_write(at::Tensor qkv, at::Tensor positions, at::Tensor cos_sin,
                   cos_sin.size(1) == head_dim,
               "cos_sin must be fp32 [max_pos, head_dim]");
   const bool kv8 = check_kv_caches(k_cache, v_cache, nkv, head_dim);
+  const float* ki = kv_scale_ptr(k_inv, k_cache, kv8, nkv, "k_inv");
+  const float* vi = kv_scale_ptr(v_inv, k_cache, kv8, nkv, "v_inv");
   TORCH_CHECK(qkv.size(1) >= (nq + 2 * nkv) * head_dim, "qkv width");
   const int tokens = (int)qkv.size(0);
   TORCH_CHECK(positions.numel() >= tokens && slot_mapping.numel() >= tokens, "metadata length");
@@ -212,19 +230,23 @@ void rope_kv_write(at::Tensor qkv, at::Tensor positions, at::Tensor cos_sin,
                             cos_sin.data_ptr<float>(), slot_mapping.data_ptr<int>(),
                             k_cache.data_ptr(), v_cache.data_ptr(), tokens, (int)nq, (int)nkv,
                             (int)head_dim, (int)k_cache.size(2), (int)cos_sin.size(0),
-                            (int)(k_cache.size(0) * k_cache.size(2)), kv8 ? 1 : 0, cur_stream()),
+                            (int)(k_cache.size(0) * k_cache.size(2)), kv8 ? 1 : 0, ki, vi,
+                            cur_stream()),
            "rope_kv_write");
 }
 
 void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                             at::Tensor block_tables, at::Tensor seq_lens, at::Tensor tmp_out,
                             at::Tensor tmp_ml, int64_t nq, int64_t nkv, int64_t head_dim,
-                            double scale, c10::optional<at::Tensor> counters, int64_t piece) {
+                            double scale, c10::optional<at::Tensor> counters, int64_t piece,
+                            c10::optional<at::Tensor> k_scale, c10::optional<at::Tensor> v_scale) {
   check_bf16(out, "out");
   check_bf16(q, "q");
   check_rows(out, "out");
   check_rows(q, "q");
   const bool kv8 = check_kv_caches(k_cache, v_cache, nkv, head_dim);
+  const float* ks = kv_scale_ptr(k_scale, k_cache, kv8, nkv, "k_scale");
+  const float* vs = kv_scale_ptr(v_scale, k_cache, kv8, nkv, "v_scale");
   check_i32(block_tables, "block_tables");
   check_i32(seq_lens, "seq_lens");
   const int batch = (int)q.size(0);
@@ -259,7 +281,7 @@ void paged_decode_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at
                                      seq_lens.data_ptr<int>(), batch, (int)nq, (int)nkv,
                                      (int)head_dim, (int)k_cache.size(2), (float)scale, cnt,
                                      (int)piece, (int)std::min<int64_t>(slot_cap, INT32_MAX),
-                                     (int)k_cache.size(0), kv8 ? 1 : 0,
+                                     (int)k_cache.size(0), kv8 ? 1 : 0, ks, vs,
                                      cur_stream()),
            "paged_decode_attention");
 }
@@ -269,12 +291,15 @@ void prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Ten
                        at::Tensor tile_info, int64_t num_tiles, int64_t nq, int64_t nkv,
                        int64_t head_dim, double scale, c10::optional<at::Tensor> part_o,
                        c10::optional<at::Tensor> part_ml, c10::optional<at::Tensor> combine,
-                       int64_t num_combine, int64_t num_partials, bool invariant) {
+                       int64_t num_combine, int64_t num_partials, bool invariant,
+                       c10::optional<at::Tensor> k_scale, c10::optional<at::Tensor> v_scale) {
   check_bf16(out, "out");
   check_bf16(q, "q");
   check_rows(out, "out");
   check_rows(q, "q");
   const bool kv8 = check_kv_caches(k_cache, v_cache, nkv, head_dim);
+  const float* ks = kv_scale_ptr(k_scale, k_cache, kv8, nkv, "k_scale");
+  const float* vs = kv_scale_ptr(v_scale, k_cache, kv8, nkv, "v_scale");
   check_i32(block_tables, "block_tables");
   check_i32(seq_lens, "seq_lens");
   check_i32(q_start_loc, "q_start_loc");
@@ -309,7 +334,7 @@ void prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Ten
                                 tile_info.data_ptr<int>(), (int)num_tiles, (int)nq, (int)nkv,
                                 (int)head_dim, (int)k_cache.size(2), (float)scale, po, pml, cb,
                                 (int)num_combine, (int)invariant, (int)k_cache.size(0), kv8 ? 1 : 0,
-                                cur_stream()),
+                                ks, vs, cur_stream()),
            "prefill_attention");
 }
 
@@ -845,7 +870,8 @@ void slab_store(at::Tensor ws, int64_t splits, int64_t rows, int64_t cols, at::T
 void slab_rope_kv(at::Tensor ws, int64_t splits, int64_t rows, int64_t cols, at::Tensor q_out,
                   at::Tensor positions, at::Tensor cos_sin, at::Tensor slot_mapping,
                   at::Tensor k_cache, at::Tensor v_cache, int64_t nq, int64_t nkv,
-                  int64_t head_dim, c10::optional<at::Tensor> residual, double eps) {
+                  int64_t head_dim, c10::optional<at::Tensor> residual, double eps,
+                  c10::optional<at::Tensor> k_inv, c10::optional<at::Tensor> v_inv) {
   check_ws(ws, splits * rows * cols);
   const void* rp = nullptr;
   int hidden = 0;
@@ -863,6 +889,8 @@ void slab_rope_kv(at::Tensor ws, int64_t splits, int64_t rows, int64_t cols, at:
   TORCH_CHECK(q_out.size(0) >= rows && q_out.size(1) >= nq * head_dim, "q_out shape");
   TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.size(1) == head_dim, "cos_sin");
   const bool kv8 = check_kv_caches(k_cache, v_cache, nkv, head_dim);
+  const float* ki = kv_scale_ptr(k_inv, k_cache, kv8, nkv, "k_inv");
+  const float* vi = kv_scale_ptr(v_inv, k_cache, kv8, nkv, "v_inv");
   TORCH_CHECK(positions.numel() >= rows && slot_mapping.numel() >= rows, "metadata length");
   check_rc(ft_slab_rope_kv(ws.data_ptr<float>(), (int)splits, (int)rows, (int)cols,
                            q_out.data_ptr(), (int)q_out.stride(0), positions.data_ptr<int>(),
@@ -870,7 +898,7 @@ void slab_rope_kv(at::Tensor ws, int64_t splits, int64_t rows, int64_t cols, at:
                            k_cache.data_ptr(), v_cache.data_ptr(), (int)nq, (int)nkv,
                            (int)head_dim, (int)k_cache.size(2), rp, hidden, (float)eps,
                            (int)cos_sin.size(0), (int)(k_cache.size(0) * k_cache.size(2)),
-                           kv8 ? 1 : 0, cur_stream()), "slab_rope_kv");
+                           kv8 ? 1 : 0, ki, vi, cur_stream()), "slab_rope_kv");
 }
 
 #if defined(FT_KERNEL_CHECKS) && FT_KERNEL_CHECKS
@@ -914,11 +942,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm", &rmsnorm);
   m.def("fused_add_rmsnorm", &fused_add_rmsnorm);
   m.def("silu_mul", &silu_mul);
-  m.def("rope_kv_write", &rope_kv_write);
+  m.def("rope_kv_write", &rope_kv_write, py::arg("qkv"), py::arg("positions"), py::arg("cos_sin"),
+        py::arg("slot_mapping"), py::arg("k_cache"), py::arg("v_cache"), py::arg("nq"),
+        py::arg("nkv"), py::arg("head_dim"), py::arg("k_inv") = py::none(),
+        py::arg("v_inv") = py::none());
   m.def("paged_decode_attention", &paged_decode_attention, py::arg("out"), py::arg("q"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"), py::arg("seq_lens"),
         py::arg("tmp_out"), py::arg("tmp_ml"), py::arg("nq"), py::arg("nkv"), py::arg("head_dim"),
-        py::arg("scale"), py::arg("counters") = py::none(), py::arg("piece") = 0);
+        py::arg("scale"), py::arg("counters") = py::none(), py::arg("piece") = 0,
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("decode_waves", []() { return ft_decode_waves(); });
   m.def("decode_max_batch", []() { return ft_decode_max_batch(); });
   m.def("prefill_attention", &prefill_attention, py::arg("out"), py::arg("q"), py::arg("k_cache"),
@@ -926,7 +958,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tile_info"), py::arg("num_tiles"), py::arg("nq"), py::arg("nkv"),
         py::arg("head_dim"), py::arg("scale"), py::arg("part_o") = py::none(),
         py::arg("part_ml") = py::none(), py::arg("combine") = py::none(),
-        py::arg("num_combine") = 0, py::arg("num_partials") = 0, py::arg("invariant") = false);
+        py::arg("num_combine") = 0, py::arg("num_partials") = 0, py::arg("invariant") = false,
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("prefill_tile_tokens", [](int64_t nq, int64_t nkv) { return ft_prefill_tile_tokens((int)nq, (int)nkv); });
   m.def("sample", &sample, py::arg("out_tokens"), py::arg("logits"), py::arg("temperature"),
         py::arg("top_p"), py::arg("top_k"), py::arg("seeds"), py::arg("steps"),
@@ -978,5 +1011,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cols"), py::arg("q_out"), py::arg("positions"), py::arg("cos_sin"),
         py::arg("slot_mapping"), py::arg("k_cache"), py::arg("v_cache"), py::arg("nq"),
         py::arg("nkv"), py::arg("head_dim"), py::arg("residual") = py::none(),
-        py::arg("eps") = 0.0);
+        py::arg("eps") = 0.0, py::arg("k_inv") = py::none(), py::arg("v_inv") = py::none());
 }

@@ -61,9 +61,10 @@ __device__ __forceinline__ uint4 store8(const float (&f)[8]) {
 }
 
 // fp8 KV cache (OCP e4m3, torch.float8_e4m3fn; ENGINE_KV_CACHE_DTYPE=fp8).  Stored
-// value = x at a per-tensor scale of 1 (vLLM's uncalibrated default), clamped to the
-// format's +-448 first: gfx950's v_cvt_pk_fp8_f32 turns an out-of-range value into
-// NaN, not the max (bench/probes/fp8_cvt_check.py, measured).  Reads widen straight
+// value = x / scale with one fp32 scale per layer and kv head (ENGINE_KV_SCALES; the
+// writers multiply by its host-computed reciprocal, absent = 1: vLLM's uncalibrated
+// default), clamped to the format's +-448 after the scaling: gfx950's
+// v_cvt_pk_fp8_f32 turns an out-of-range value into NaN, not the max (bench/probes/fp8_cvt_check.py, measured).  Reads widen straight
 // to bf16 MFMA operands with v_cvt_scalef32_pk_bf16_fp8 (2 values per op; its scale
 // operand is exact for powers of two only -- probe -- so it stays 1).
 constexpr float kFp8Max = 448.f;

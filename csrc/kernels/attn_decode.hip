@@ -164,8 +164,12 @@ __device__ __forceinline__ void mt_load8(MTile8<D>& t, const uint8_t* __restrict
 // in-launch combine by the last arriving wave (see the header comment).
 // whole: this wave covered the segment alone; otherwise its partial goes to slot
 // `slot` and the segment's np partials sit at slots first .. first + np - 1.
+// vs: the kv head's V scale (fp8 caches; 1 otherwise), applied once where the output
+// is divided by l -- never to the fp32 partials: it is uniform over the segment, so
+// it commutes with the merge.
 template <int D, int G, int ND, bool FC>
-__device__ __forceinline__ void dec_finish(floatx4_t (&o)[ND], float l_run, float m_run, int b, int h,
+__device__ __forceinline__ void dec_finish(floatx4_t (&o)[ND], float l_run, float m_run, float vs,
+                                           int b, int h,
                                            bool whole, int slot_i, int first, int np, int nkv,
                                            uint16_t* __restrict__ out, int out_stride,
                                            float* __restrict__ tmp_out, float* __restrict__ tmp_ml,
@@ -180,7 +184,7 @@ __device__ __forceinline__ void dec_finish(floatx4_t (&o)[ND], float l_run, floa
       const int r = 4 * g + i4;
       const float lr = __shfl(l_tot, r & 15, 64);
       if (r < G) {
-        const float inv = 1.f / lr;
+        const float inv = 1.f / lr * vs;
         uint16_t* op = out + (size_t)b * out_stride + (h * G + r) * D + n;
 #pragma unroll
         for (int nd = 0; nd < ND; ++nd) op[nd * 16] = f32_to_bf16(o[nd][i4] * inv);
@@ -270,7 +274,7 @@ __device__ __forceinline__ void dec_finish(floatx4_t (&o)[ND], float l_run, floa
               }
             }
           }
-          const float inv = 1.f / den;
+          const float inv = 1.f / den * vs;
 #pragma unroll
           for (int nd = 0; nd < ND; ++nd) op[r * D + 16 * nd + c] = f32_to_bf16(acc[nd] * inv);
         }
@@ -287,8 +291,9 @@ __global__ __launch_bounds__(256, WPC) void paged_decode_kernel(
     float* __restrict__ tmp_ml, const uint16_t* __restrict__ q, int q_stride,
     uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
     const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ seq_lens,
-    int batch, int nkv, int bs_shift, float scale_log2, int* __restrict__ counters,
-    int min_tiles, int piece, int slot_cap, int num_blocks) {
+    int batch, int nkv, int bs_shift, float scale_log2_in, int* __restrict__ counters,
+    int min_tiles, int piece, int slot_cap, int num_blocks, const float* __restrict__ k_scale,
+    const float* __restrict__ v_scale) {
   static_assert(G >= 1 && G <= 16, "GQA group must fit the 16 MFMA columns");
   constexpr int KC = D / 32, ND = D / 16;
   // s_pre: tile prefix; s_pre + kDecMaxBatch + 1: piece prefix (piece mode)
@@ -315,7 +320,6 @@ __global__ __launch_bounds__(256, WPC) void paged_decode_kernel(
   if (total == 0 || w >= nw) return;
 
   const int lane = lane_id();
-  const float thr_raw = kDecRescaleThr / scale_log2;   // the threshold in raw score units
   const int n = lane & 15;   // MFMA column (head) / row (token) / dim within a tile
   const int g = lane >> 4;   // k group
   const int bsz = 1 << bs_shift;
@@ -332,6 +336,21 @@ __global__ __launch_bounds__(256, WPC) void paged_decode_kernel(
   // tiles [t0, t0 + cnt) of segment (b, h), then dec_finish
   auto run = [&](int b, int h, int t0, int cnt, int nb, bool whole, int slot_i, int first, int np) {
     const int L = seq_lens[b];
+    // fp8 caches: stored = x / scale per kv head (k_scale / v_scale fp32 [nkv], null =
+    // 1.0).  K's scale folds into the softmax scale of this segment -- raw scores are
+    // in stored units, so the threshold, nbias, alpha and the m handed to dec_finish
+    // all use the per-head value and partial maxima stay in scaled log2 units; V's
+    // scale multiplies the normalised output once (dec_finish).  h is wave-uniform:
+    // scalar loads, once per segment, nothing added to the tile loop.  The loads are
+    // issued here and first used below the Q loads, so their latency hides behind
+    // those (a wait right here cost 1.5 us at 50 x 1.5-3k, where a wave runs 1-2
+    // short segments: profiles/kv_scales_r07.log).
+    float ksv = 1.f, vs = 1.f;
+    if constexpr (KV8) {
+      const int hu = __builtin_amdgcn_readfirstlane(h);
+      if (k_scale != nullptr) ksv = k_scale[hu];
+      if (v_scale != nullptr) vs = v_scale[hu];
+    }
 
     // Q^T fragments (B operand): lane (g, n) = head n of this kv head, dims 8g.. (+32 kc)
     uint4 qb[KC];
@@ -348,6 +367,8 @@ __global__ __launch_bounds__(256, WPC) void paged_decode_kernel(
     float m_run = -INFINITY;   // reference max of head n, raw score units (uniform over g)
     float l_run = 0.f;         // this lane's share of the running sum of head n
     float nbias = 0.f;         // -m_run * scale_log2
+    const float scale_log2 = KV8 ? scale_log2_in * ksv : scale_log2_in;
+    const float thr_raw = kDecRescaleThr / scale_log2;   // the threshold in raw score units
 
     const int* bt = block_tables + (size_t)b * bt_stride;
     for (int c0 = 0; c0 < cnt; c0 += 64) {
@@ -442,7 +463,7 @@ __global__ __launch_bounds__(256, WPC) void paged_decode_kernel(
       }
     }
 
-    dec_finish<D, G, ND, FC>(o, l_run, m_run * scale_log2, b, h, whole, slot_i, first, np, nkv, out,
+    dec_finish<D, G, ND, FC>(o, l_run, m_run * scale_log2, vs, b, h, whole, slot_i, first, np, nkv, out,
                              out_stride, tmp_out, tmp_ml, counters, lane, g, n);
   };
   // b = last sequence with nkv * pre[b] <= f
@@ -498,7 +519,7 @@ template <int D, int G>
 __global__ __launch_bounds__(256) void paged_decode_combine_kernel(
     uint16_t* __restrict__ out, int out_stride, const float* __restrict__ tmp_out,
     const float* __restrict__ tmp_ml, const int* __restrict__ seq_lens, int batch, int nkv,
-    int nw_grid, int min_tiles) {
+    int nw_grid, int min_tiles, const float* __restrict__ v_scale) {
   __shared__ int s_pre[kDecMaxBatch + 1];
   __shared__ float s_M[G], s_den[G];
   if (wave_id() == 0) dec_prefix(s_pre, seq_lens, batch, 1);
@@ -520,6 +541,7 @@ __global__ __launch_bounds__(256) void paged_decode_combine_kernel(
   if (np <= 1) return;  // one wave covered it and wrote bf16 directly
   const size_t base = (size_t)(seg + wf);
   const int lane = lane_id();
+  const float vs = v_scale ? v_scale[h] : 1.f;   // fp8 caches: the kv head's V scale
   for (int g = wave_id(); g < G; g += blockDim.x / 64) {
     float M = -INFINITY;
     for (int k = lane; k < np; k += 64) M = fmaxf(M, tmp_ml[((base + k) * G + g) * 2]);
@@ -548,7 +570,7 @@ __global__ __launch_bounds__(256) void paged_decode_combine_kernel(
       const size_t s0 = (base + k) * G + g;
       a0 += exp2f(tmp_ml[s0 * 2] - M) * tmp_out[s0 * D + d];
     }
-    o[i] = f32_to_bf16((a0 + a1) / s_den[g]);
+    o[i] = f32_to_bf16((a0 + a1) / s_den[g] * vs);
   }
 }
 
@@ -592,8 +614,10 @@ extern "C" int ft_paged_decode_attention(void* out, int out_stride, float* tmp_o
                                          int bt_stride, const int* seq_lens, int batch, int nq,
                                          int nkv, int head_dim, int block_size, float scale,
                                          int* counters, int piece, int slot_cap,
-                                         int num_blocks, int kv8, hipStream_t stream) {
+                                         int num_blocks, int kv8, const float* k_scale,
+                                         const float* v_scale, hipStream_t stream) {
   if (batch <= 0) return 0;
+  if (!kv8 && (k_scale != nullptr || v_scale != nullptr)) return -7;  // scales: fp8 caches only
   if (nq % nkv != 0) return -1;
   if (piece < 0 || (piece > 0 && counters == nullptr)) return -6;  // pieces merge in-launch
   if (batch > ft::kDecMaxBatch) return -5;
@@ -651,7 +675,7 @@ extern "C" int ft_paged_decode_attention(void* out, int out_stride, float* tmp_o
 #define FT_DEC_ARGS                                                                             \
   (uint16_t*)out, out_stride, tmp_out, tmp_ml, (const uint16_t*)q, q_stride, (uint16_t*)k_cache, \
       (uint16_t*)v_cache, block_tables, bt_stride, seq_lens, batch, nkv, bs_shift, scale_log2,   \
-      counters, min_tiles, piece, slot_cap, num_blocks
+      counters, min_tiles, piece, slot_cap, num_blocks, k_scale, v_scale
 #define FT_DEC_LAUNCH(DD, GG, RR, FCC)                                                  \
   if (wpc == 1)                                                                                \
     hipLaunchKernelGGL((ft::paged_decode_kernel<DD, GG, RR, FCC, 1>), dim3(nwg), dim3(64 * nwv), \
@@ -681,7 +705,7 @@ extern "C" int ft_paged_decode_attention(void* out, int out_stride, float* tmp_o
                            dim3(64 * nwv8), 0, stream, FT_DEC_ARGS);                            \
         hipLaunchKernelGGL((ft::paged_decode_combine_kernel<DD, GG>), dim3(batch * nkv), dim3(256),\
                            0, stream, (uint16_t*)out, out_stride, tmp_out, tmp_ml, seq_lens, batch,\
-                           nkv, nwg * nwv8, min_tiles);                                         \
+                           nkv, nwg * nwv8, min_tiles, v_scale);                                       \
       }                                                                                        \
       return static_cast<int>(hipGetLastError());                                              \
     }                                                                                          \
@@ -695,7 +719,7 @@ extern "C" int ft_paged_decode_attention(void* out, int out_stride, float* tmp_o
       FT_DEC_LAUNCH(DD, GG, RR, false);                                                        \
       hipLaunchKernelGGL((ft::paged_decode_combine_kernel<DD, GG>), dim3(batch * nkv), dim3(256),\
                          0, stream, (uint16_t*)out, out_stride, tmp_out, tmp_ml, seq_lens, batch,\
-                         nkv, nwg * nwv, min_tiles);                                             \
+                         nkv, nwg * nwv, min_tiles, v_scale);                                           \
     }                                                                                            \
     return static_cast<int>(hipGetLastError());                                                  \
   }

@@ -68,15 +68,20 @@ __device__ __forceinline__ float kgroup_sum(float v) { return kgroups_sum(v); }
 // loads one 16-B piece of fp8 K rows and one of V^T rows (16 elements each), widens
 // them to bf16 (ft_common.h fp8x8_to_bf16) and writes two 16-B chunks at their
 // swizzled slots.  Two tiles are in flight in registers (loaded two iterations ahead)
-// over two LDS slots; one barrier per tile.
+// over two LDS slots; one barrier per tile.  k_scale / v_scale (KV8 only, fp32 [nkv],
+// null = 1.0): stored = x / scale per kv head.  A workgroup's 256 rows belong to one kv
+// head, so K's scale folds into scale_log2 (threshold, alpha, nbias and the m stored
+// in part_ml all use the per-head value; partial maxima stay in scaled log2 units)
+// and V's scale multiplies the output once where it is normalised (here for unsplit
+// items, in prefill_combine_kernel for split ones) -- nothing is added to the tile loop.
 template <int D, int G, bool INV, bool KV8 = false>
 __global__ __launch_bounds__(512, 1) void prefill_attn_kernel(
     uint16_t* __restrict__ out, int out_stride, const uint16_t* __restrict__ q, int q_stride,
     const uint16_t* __restrict__ k_cache, const uint16_t* __restrict__ v_cache,
     const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ seq_lens,
     const int* __restrict__ q_start_loc, const int* __restrict__ tile_info, int nkv,
-    int block_size, float scale_log2, float* __restrict__ part_o, float* __restrict__ part_ml,
-    int num_blocks) {
+    int block_size, float scale_log2_in, float* __restrict__ part_o, float* __restrict__ part_ml,
+    int num_blocks, const float* __restrict__ k_scale, const float* __restrict__ v_scale) {
   constexpr int NCH = D / 8;          // 16-B chunks per K row
   constexpr int KC = D / 32;          // k-steps of S^T = K Q^T
   constexpr int ND = D / 16;          // 16-row dim tiles of O^T
@@ -94,6 +99,11 @@ __global__ __launch_bounds__(512, 1) void prefill_attn_kernel(
 
   const int tile = blockIdx.x;
   const int kvh = blockIdx.y;
+  float scale_log2 = scale_log2_in, vs = 1.f;
+  if constexpr (KV8) {   // blockIdx.y is wave-uniform: scalar loads
+    if (k_scale != nullptr) scale_log2 = scale_log2_in * k_scale[kvh];
+    if (v_scale != nullptr) vs = v_scale[kvh];
+  }
   // work item: (sequence, first query token, KV tile range lo << 16 | hi, partial slot)
   const int b = tile_info[tile * 4];
   const int qs = tile_info[tile * 4 + 1];
@@ -443,7 +453,7 @@ __global__ __launch_bounds__(512, 1) void prefill_attn_kernel(
       continue;
     }
     const int tq = r / G, g = r - (r / G) * G;
-    const float inv = l > 0.f ? 1.f / l : 0.f;
+    const float inv = l > 0.f ? 1.f / l * vs : 0.f;
     uint16_t* op = out + (size_t)(q0 + qs + tq) * out_stride + (kvh * G + g) * D + 4 * lg;
 #pragma unroll
     for (int nd = 0; nd < ND; ++nd)
@@ -462,7 +472,7 @@ template <int D, int G>
 __global__ __launch_bounds__(256) void prefill_combine_kernel(
     uint16_t* __restrict__ out, int out_stride, const float* __restrict__ part_o,
     const float* __restrict__ part_ml, const int* __restrict__ q_start_loc,
-    const int* __restrict__ combine, int nkv) {
+    const int* __restrict__ combine, int nkv, const float* __restrict__ v_scale) {
   constexpr int QB = kPrefillRows / G;
   constexpr int CH = D / 4;                 // float4 chunks per row
   constexpr int RPB = 256 / CH;             // rows per workgroup
@@ -501,7 +511,8 @@ __global__ __launch_bounds__(256) void prefill_combine_kernel(
     v = v_n;
     row += stride;
   }
-  const float inv = den > 0.f ? 1.f / den : 0.f;
+  // fp8 caches: the kv head's V scale, once, on the merged output
+  const float inv = den > 0.f ? 1.f / den * (v_scale ? v_scale[kvh] : 1.f) : 0.f;
   const int tq = r / G, g = r - (r / G) * G;
   *reinterpret_cast<uint2*>(out + (size_t)(q0 + qs + tq) * out_stride + (kvh * G + g) * D + 4 * ch) =
       make_uint2(pack2(acc.x * inv, acc.y * inv), pack2(acc.z * inv, acc.w * inv));
@@ -518,8 +529,10 @@ extern "C" int ft_prefill_attention(void* out, int out_stride, const void* q, in
                                     int nq, int nkv, int head_dim, int block_size, float scale,
                                     float* part_o, float* part_ml, const int* combine,
                                     int num_combine, int invariant, int num_blocks, int kv8,
+                                    const float* k_scale, const float* v_scale,
                                     hipStream_t stream) {
   if (num_tiles <= 0) return 0;
+  if (!kv8 && (k_scale != nullptr || v_scale != nullptr)) return -7;  // scales: fp8 caches only
   if (nq % nkv != 0) return -1;
   if (num_combine > 0 && (part_o == nullptr || part_ml == nullptr || combine == nullptr)) return -3;
   const int G = nq / nkv;
@@ -532,30 +545,30 @@ extern "C" int ft_prefill_attention(void* out, int out_stride, const void* q, in
                          (uint16_t*)out, out_stride, (const uint16_t*)q, q_stride,           \
                          (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,   \
                          bt_stride, seq_lens, q_start_loc, tile_info, nkv, block_size,       \
-                         scale_log2, part_o, part_ml, num_blocks);                           \
+                         scale_log2, part_o, part_ml, num_blocks, k_scale, v_scale);         \
     else if (kv8)                                                                            \
       hipLaunchKernelGGL((ft::prefill_attn_kernel<DD, GG, false, true>), grid, block, 0, stream, \
                          (uint16_t*)out, out_stride, (const uint16_t*)q, q_stride,           \
                          (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,   \
                          bt_stride, seq_lens, q_start_loc, tile_info, nkv, block_size,       \
-                         scale_log2, part_o, part_ml, num_blocks);                           \
+                         scale_log2, part_o, part_ml, num_blocks, k_scale, v_scale);         \
     else if (invariant)                                                                      \
       hipLaunchKernelGGL((ft::prefill_attn_kernel<DD, GG, true>), grid, block, 0, stream,    \
                          (uint16_t*)out, out_stride, (const uint16_t*)q, q_stride,           \
                          (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,   \
                          bt_stride, seq_lens, q_start_loc, tile_info, nkv, block_size,       \
-                         scale_log2, part_o, part_ml, num_blocks);                           \
+                         scale_log2, part_o, part_ml, num_blocks, k_scale, v_scale);         \
     else                                                                                     \
       hipLaunchKernelGGL((ft::prefill_attn_kernel<DD, GG, false>), grid, block, 0, stream,   \
                          (uint16_t*)out, out_stride, (const uint16_t*)q, q_stride,           \
                          (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables,   \
                          bt_stride, seq_lens, q_start_loc, tile_info, nkv, block_size,       \
-                         scale_log2, part_o, part_ml, num_blocks);                           \
+                         scale_log2, part_o, part_ml, num_blocks, k_scale, v_scale);         \
     if (num_combine > 0)                                                                     \
       hipLaunchKernelGGL((ft::prefill_combine_kernel<DD, GG>),                               \
                          dim3(num_combine, nkv, ft::kPrefillRows / (256 / (DD / 4))),         \
                          dim3(256), 0, stream, (uint16_t*)out, out_stride, part_o, part_ml,  \
-                         q_start_loc, combine, nkv);                                         \
+                         q_start_loc, combine, nkv, v_scale);                                \
     return static_cast<int>(hipGetLastError());                                              \
   }
   FT_PF_CASE(128, 1)

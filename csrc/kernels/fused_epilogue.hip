@@ -142,14 +142,15 @@ __global__ __launch_bounds__(256) void slab_store_kernel(SrcSlab src, uint16_t* 
 // ---------------------------------------------------------------------------------
 // RoPE + paged KV write from split-K slabs of the QKV projection
 // ---------------------------------------------------------------------------------
-// KV8: fp8 (e4m3) caches (ft_common.h fp8x*), same layouts with 1-byte elements
+// KV8: fp8 (e4m3) caches (ft_common.h fp8x*), same layouts with 1-byte elements;
+// k_inv / v_inv: per-head reciprocal scales as in rope_kv.hip (KV8 only, null = 1.0)
 template <int D, bool KV8>
 __global__ __launch_bounds__(256) void slab_rope_kv_kernel(
     SrcSlab src, uint16_t* __restrict__ q_out, int q_stride, const int* __restrict__ positions,
     const float* __restrict__ cos_sin, const int* __restrict__ slot_mapping,
     void* __restrict__ k_cache, void* __restrict__ v_cache, int nq, int nkv,
     int block_size, const uint16_t* __restrict__ residual, int hidden, float eps, int cos_rows,
-    int num_slots) {
+    int num_slots, const float* __restrict__ k_inv, const float* __restrict__ v_inv) {
   constexpr int HALF = D / 2;
   constexpr int CPH = HALF / 8;
   const int t = blockIdx.x;
@@ -201,6 +202,12 @@ __global__ __launch_bounds__(256) void slab_rope_kv_kernel(
     } else if (slot >= 0) {
       const size_t e = (((size_t)blk * nkv + (head - nq)) * block_size + off) * D;
       if constexpr (KV8) {
+        const float ki = k_inv ? k_inv[head - nq] : 1.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          y1[j] *= ki;
+          y2[j] *= ki;
+        }
         uint8_t* kp = reinterpret_cast<uint8_t*>(k_cache) + e;
         *reinterpret_cast<uint2*>(kp + c * 8) = fp8x8_pack(y1);
         *reinterpret_cast<uint2*>(kp + HALF + c * 8) = fp8x8_pack(y2);
@@ -222,6 +229,9 @@ __global__ __launch_bounds__(256) void slab_rope_kv_kernel(
       // V blocks are transposed ([D][block_size], rope_kv.hip)
       const size_t e = (((size_t)blk * nkv + kh) * D + c * 8) * block_size + off;
       if constexpr (KV8) {
+        const float vi = v_inv ? v_inv[kh] : 1.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] *= vi;
         const uint2 q8 = fp8x8_pack(f);
         uint8_t* vp = reinterpret_cast<uint8_t*>(v_cache) + e;
 #pragma unroll
@@ -311,7 +321,7 @@ extern "C" int ft_slab_rope_kv(const float* ws, int splits, int rows, int cols, 
                                const int* slot_mapping, void* k_cache, void* v_cache, int nq,
                                int nkv, int head_dim, int block_size, const void* residual,
                                int hidden, float eps, int cos_rows, int num_slots, int kv8,
-                               hipStream_t stream) {
+                               const float* k_inv, const float* v_inv, hipStream_t stream) {
   if (rows <= 0) return 0;
   if (residual != nullptr && hidden % 8 != 0) return -2;
   ft::SrcSlab src{ws, splits, rows, cols};
@@ -319,7 +329,7 @@ extern "C" int ft_slab_rope_kv(const float* ws, int splits, int rows, int cols, 
   hipLaunchKernelGGL((ft::slab_rope_kv_kernel<DD, K8>), dim3(rows, 2), dim3(256), 0, stream, src, \
                      (uint16_t*)q_out, q_stride, positions, cos_sin, slot_mapping, k_cache,       \
                      v_cache, nq, nkv, block_size, (const uint16_t*)residual, hidden, eps,        \
-                     cos_rows, num_slots)
+                     cos_rows, num_slots, k_inv, v_inv)
   if (head_dim == 128) {
     if (kv8) FT_SRK(128, true); else FT_SRK(128, false);
   } else if (head_dim == 64) {

@@ -18,7 +18,9 @@
 
 namespace ft {
 
-// KV8: fp8 (e4m3) caches, same layouts with 1-byte elements (ft_common.h fp8x*)
+// KV8: fp8 (e4m3) caches, same layouts with 1-byte elements (ft_common.h fp8x*).
+// k_inv / v_inv (KV8 only; null = 1.0): fp32 [nkv] reciprocals of the per-head scales,
+// stored = clamp(x * inv, +-448).  x * 1.0f is exact, so one body serves both cases.
 template <int D, bool KV8>
 __global__ __launch_bounds__(256) void rope_kv_kernel(uint16_t* __restrict__ qkv, int qkv_stride,
                                                       const int* __restrict__ positions,
@@ -27,7 +29,9 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(uint16_t* __restrict__ qkv
                                                       void* __restrict__ k_cache,
                                                       void* __restrict__ v_cache, int nq,
                                                       int nkv, int block_size, int cos_rows,
-                                                      int num_slots) {
+                                                      int num_slots,
+                                                      const float* __restrict__ k_inv,
+                                                      const float* __restrict__ v_inv) {
   constexpr int HALF = D / 2;
   constexpr int CPH = HALF / 8;  // 8-pair chunks per head
   const int t = blockIdx.x;
@@ -69,6 +73,12 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(uint16_t* __restrict__ qkv
       const int blk = slot / block_size, off = slot - blk * block_size;
       const size_t e = (((size_t)blk * nkv + kh) * block_size + off) * D;
       if constexpr (KV8) {
+        const float ki = k_inv ? k_inv[kh] : 1.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          y1[j] *= ki;
+          y2[j] *= ki;
+        }
         uint8_t* kp = reinterpret_cast<uint8_t*>(k_cache) + e;
         reinterpret_cast<uint2*>(kp + c * 8)[0] = fp8x8_pack(y1);
         reinterpret_cast<uint2*>(kp + HALF + c * 8)[0] = fp8x8_pack(y2);
@@ -91,6 +101,9 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(uint16_t* __restrict__ qkv
       if constexpr (KV8) {
         float f[8];
         load8(v, f);
+        const float vi = v_inv ? v_inv[kh] : 1.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] *= vi;
         const uint2 q8 = fp8x8_pack(f);
         uint8_t* vp = reinterpret_cast<uint8_t*>(v_cache) + e;
 #pragma unroll
@@ -114,13 +127,14 @@ extern "C" int ft_rope_kv_write(void* qkv, int qkv_stride, const int* positions,
                                 const float* cos_sin, const int* slot_mapping, void* k_cache,
                                 void* v_cache, int tokens, int nq, int nkv, int head_dim,
                                 int block_size, int cos_rows, int num_slots, int kv8,
+                                const float* k_inv, const float* v_inv,
                                 hipStream_t stream) {
   if (tokens <= 0) return 0;
   dim3 grid(tokens), block(256);
 #define FT_ROPE(DD, K8)                                                                     \
   hipLaunchKernelGGL((ft::rope_kv_kernel<DD, K8>), grid, block, 0, stream, (uint16_t*)qkv,  \
                      qkv_stride, positions, cos_sin, slot_mapping, k_cache, v_cache, nq, nkv, \
-                     block_size, cos_rows, num_slots)
+                     block_size, cos_rows, num_slots, k_inv, v_inv)
   if (head_dim == 128) {
     if (kv8) FT_ROPE(128, true); else FT_ROPE(128, false);
   } else if (head_dim == 64) {

@@ -67,10 +67,36 @@ class EngineConfig:
     # a sequence's tokens independent of what else shares its steps (fixed GEMM splits,
     # fixed-piece attention partitions; TP=1, bf16; slower decode attention)
     batch_invariant: bool = False
-    # KV-cache storage: "auto" (the compute dtype) | "fp8" (OCP e4m3 at scale 1, vLLM's
-    # --kv-cache-dtype fp8 without calibration): half the cache bytes per token, so the
-    # decode attention stream halves and the pool holds twice the tokens
+    # KV-cache storage: "auto" (the compute dtype) | "fp8" (OCP e4m3, vLLM's
+    # --kv-cache-dtype fp8): half the cache bytes per token, so the decode attention
+    # stream halves and the pool holds twice the tokens
     kv_cache_dtype: str = "auto"
+    # fp8 KV only: per-layer, per-head K / V scales (stored = x / scale).  "auto": the
+    # checkpoint's k_scale / v_scale when it has them, else 1.0 | "one": always 1.0 |
+    # "calibrate": one prefill of a built-in chat prompt at start-up | a .json path
+    # ({"k": [[nkv floats] per layer], "v": ...}; LLMEngine.save_kv_scales writes one)
+    kv_scales: str = "auto"
+
+    def __post_init__(self):
+        self.check_kv_scales()
+
+    def check_kv_scales(self) -> str:
+        """auto | one | calibrate | file; ValueError for anything else, and for a value
+        other than auto / one with a KV cache that is not fp8."""
+        v = (self.kv_scales or "auto").strip()
+        low = v.lower()
+        if low in ("auto", "one", "calibrate"):
+            mode = low
+        elif low.endswith(".json"):
+            mode = "file"
+        else:
+            raise ValueError(f"kv_scales {self.kv_scales!r}: auto | one | calibrate | "
+                             "a path to a .json file")
+        fp8 = (self.kv_cache_dtype or "auto").lower() in ("fp8", "fp8_e4m3", "float8_e4m3fn", "e4m3")
+        if mode in ("calibrate", "file") and not fp8:
+            raise ValueError(f"kv_scales={self.kv_scales!r} needs kv_cache_dtype=fp8 "
+                             f"(got {self.kv_cache_dtype!r})")
+        return mode
 
     def kv_torch_dtype(self, compute_dtype):
         import torch
@@ -135,9 +161,11 @@ class EngineConfig:
             quantization=_env(["ENGINE_QUANTIZATION", "VLLM_QUANTIZATION"], None) or None,
             batch_invariant=_env(["ENGINE_BATCH_INVARIANT", "VLLM_BATCH_INVARIANT"], False, _bool),
             kv_cache_dtype=_env(["ENGINE_KV_CACHE_DTYPE", "VLLM_KV_CACHE_DTYPE"], "auto"),
+            kv_scales=_env(["ENGINE_KV_SCALES"], "auto"),
         )
         for k, v in overrides.items():
             setattr(c, k, v)
+        c.check_kv_scales()
         if c.separate_process is None:
             # a TP group runs in its own process by default: when a worker dies the
             # supervisor (parallel/dp_router.py) can tear the group down and respawn it

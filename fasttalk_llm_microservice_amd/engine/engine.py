@@ -838,6 +838,25 @@ class LLMEngine:
             g.shutdown()
             self.tp_group = None
 
+    def save_kv_scales(self, path: str):
+        """Writes the fp8 KV scales in use as the JSON file ``kv_scales=<path>`` reads:
+        {"k": [[num_kv_heads floats] per layer], "v": [...]} (calibrate once, reuse)."""
+        import torch
+
+        from . import kv_calibrate
+
+        m = getattr(self.runner, "model", None)
+        if m is None:
+            raise RuntimeError("this runner holds no model to read KV scales from")
+        if m.tp > 1:
+            raise ValueError("save_kv_scales needs all kv heads: run it at TP=1")
+        if m.kv_scales is None:
+            k = v = torch.ones(self.model_cfg.num_layers, self.model_cfg.num_kv_heads)
+        else:
+            k = torch.stack([s[0] for s in m.kv_scales]).cpu()
+            v = torch.stack([s[1] for s in m.kv_scales]).cpu()
+        kv_calibrate.save_scales_json(path, k, v)
+
     def kv_usage(self) -> float:
         n = self.bm.num_blocks
         return 1.0 - self.bm.num_free() / n if n else 0.0
@@ -853,6 +872,8 @@ class LLMEngine:
             "kv_blocks_free": self.bm.num_free(),
             "kv_blocks_cached": self.bm.num_cached(),
             "kv_usage": self.kv_usage(),
+            "kv_cache_dtype": self.cfg.kv_cache_dtype,
+            "kv_scales": dict(getattr(self.runner, "kv_scale_info", None) or {"source": "one"}),
             "prefix_cache_hit_rate": (self.bm.hits / self.bm.queries) if self.bm.queries else 0.0,
             "preemptions": self.scheduler.num_preemptions,
             "guided_capped_steps": self.scheduler.guided_capped,

@@ -218,6 +218,24 @@ class ModelRunner:
             self.model.set_batch_invariant(max(cfg.max_num_batched_tokens, cfg.max_num_seqs)
                                            + cfg.max_num_seqs)
         self.kv_dtype = cfg.kv_torch_dtype(self.dtype)
+        # fp8 KV scales (cfg.kv_scales): set on the model now -- after the weights, before
+        # the pool exists and before any graph capture; calibration frees its small
+        # temporary cache before the pool is sized
+        from . import kv_calibrate
+
+        t0 = time.time()
+        src = kv_calibrate.resolve(cfg, model_cfg, self.model, self.kv_dtype, self.max_model_len)
+        if self.is_gpu and src == "calibrate":
+            # return the calibration prefill's temporary cache and activations before the
+            # pool is sized from free memory; every other mode allocated nothing, and its
+            # pool is sized exactly as it was before scales existed
+            torch.cuda.synchronize(self.device)
+            torch.cuda.empty_cache()
+        self.kv_scale_info = self.model.kv_scale_summary()
+        if self.kv_dtype == torch.float8_e4m3fn:
+            i = self.kv_scale_info
+            log.info("fp8 KV scales: source %s, K %.4g..%.4g, V %.4g..%.4g (%.2fs)", i["source"],
+                     i["k_min"], i["k_max"], i["v_min"], i["v_max"], time.time() - t0)
         self.num_blocks = self._decide_num_blocks()
         self.kv = self.model.allocate_kv_cache(self.num_blocks, self.bs, self.kv_dtype)
         # FT_KERNEL_CHECKS=1: the bounds-checked kernel build validates every index it

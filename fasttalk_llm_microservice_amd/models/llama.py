@@ -444,6 +444,12 @@ class LlamaModel:
         # TP: all-reduce + residual add + RMSNorm in one launch (FT_TP_FUSED_NORM=0: the
         # separate slab_store -> all-reduce -> add+RMSNorm launches, for A/B runs)
         self.tp_fused_norm = os.environ.get("FT_TP_FUSED_NORM", "1") != "0"
+        # fp8 KV caches: per layer (k_scale, v_scale, k_inv, v_inv), fp32 [nkv] each, for
+        # this rank's kv heads (set_kv_scales); None = scale 1.0 everywhere
+        self.kv_scales: Optional[List[Tuple[torch.Tensor, ...]]] = None
+        self.kv_scale_source = "one"
+        # per-layer scales a checkpoint carried (load_checkpoint): (k, v) [layers, nkv]
+        self.ckpt_kv_scales: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
 
     # ------------------------------------------------------------------ weights
     def _set_layers(self, shards):
@@ -523,6 +529,10 @@ class LlamaModel:
         else:
             lm = idx.get("lm_head.weight").to(self.dtype)
         self.lm_head = W._shard_rows(lm, self.rank, self.tp).contiguous().to(self.device)
+        full_scales = W.load_kv_scales(cfg, idx)
+        if full_scales is not None:
+            self.ckpt_kv_scales = tuple(W.shard_kv_scales(cfg, t, self.rank, self.tp)
+                                        for t in full_scales)
         if not awq:  # AWQ layers arrive quantized
             self._quantize_layers()
         self._prepare_packed()
@@ -961,8 +971,52 @@ class LlamaModel:
                  torch.zeros(vs, dtype=dt, device=self.device))
                 for _ in range(self.cfg.num_layers)]
 
+    def set_kv_scales(self, k: torch.Tensor, v: torch.Tensor, source: str = "given"):
+        """Per-layer, per-head scales of fp8 KV caches: ``k`` / ``v`` [num_layers, nkv]
+        for this rank's kv heads (stored = clamp(x / scale, +-448), x = stored * scale).
+        The device tensors are allocated once and later calls copy into them in place
+        (decode graphs capture their addresses).  Allowed only while the caches hold
+        nothing: what is already stored was written at the old scales."""
+        nl = self.cfg.num_layers
+        k = torch.as_tensor(k, dtype=torch.float32).detach().cpu()
+        v = torch.as_tensor(v, dtype=torch.float32).detach().cpu()
+        for name, t in (("k", k), ("v", v)):
+            if tuple(t.shape) != (nl, self.nkv):
+                raise ValueError(f"{name} scales: shape {tuple(t.shape)}, expected {(nl, self.nkv)}")
+            if not bool(torch.isfinite(t).all()) or not bool((t > 0).all()):
+                raise ValueError(f"{name} scales must be finite and positive")
+        if self.kv_scales is None:
+            self.kv_scales = [tuple(torch.ones(self.nkv, dtype=torch.float32, device=self.device)
+                                    for _ in range(4)) for _ in range(nl)]
+        for li, (ks, vs, ki, vi) in enumerate(self.kv_scales):
+            ks.copy_(k[li])
+            vs.copy_(v[li])
+            # reciprocals on the host, in fp32: writers and reference multiply by these bits
+            ki.copy_(1.0 / k[li])
+            vi.copy_(1.0 / v[li])
+        self.kv_scale_source = source
+
+    def kv_scale_summary(self) -> Dict[str, object]:
+        """Scale source and the min / max of this rank's K and V scales (for logs, /stats)."""
+        out: Dict[str, object] = {"source": self.kv_scale_source}
+        if self.kv_scales is None:
+            out.update(k_min=1.0, k_max=1.0, v_min=1.0, v_max=1.0)
+        else:
+            k = torch.stack([s[0] for s in self.kv_scales]).cpu()
+            v = torch.stack([s[1] for s in self.kv_scales]).cpu()
+            out.update(k_min=float(k.min()), k_max=float(k.max()),
+                       v_min=float(v.min()), v_max=float(v.max()))
+        return out
+
+    def _layer_scales(self, li: int, kc):
+        """(k_scale, v_scale, k_inv, v_inv) of layer ``li`` for an fp8 cache, else Nones."""
+        if self.kv_scales is None or kc.dtype != torch.float8_e4m3fn:
+            return None, None, None, None
+        return self.kv_scales[li]
+
     # ------------------------------------------------------------------ forward
-    def _attention(self, qkv: torch.Tensor, meta: AttnMeta, kc, vc) -> torch.Tensor:
+    def _attention(self, qkv: torch.Tensor, meta: AttnMeta, kc, vc, k_scale=None,
+                   v_scale=None) -> torch.Tensor:
         """Decode rows through the paged split-K kernel, prefill rows through the
         varlen MFMA kernel; q is read from the RoPE'd qkv rows."""
         t = qkv.shape[0]
@@ -973,13 +1027,14 @@ class LlamaModel:
             ops.decode_attention(attn[:nd], qkv[:nd], kc, vc, meta.dec_block_tables,
                                  meta.dec_seq_lens, meta.tmp_out, meta.tmp_ml, nq, nkv, d,
                                  self.scale, counters=meta.dec_counters,
-                                 piece=ops.DECODE_INV_PIECE if self.invariant else 0)
+                                 piece=ops.DECODE_INV_PIECE if self.invariant else 0,
+                                 k_scale=k_scale, v_scale=v_scale)
         if t > nd:
             ops.prefill_attention(attn[nd:], qkv[nd:], kc, vc, meta.block_tables, meta.seq_lens,
                                   meta.q_start_loc, meta.tile_info, meta.num_tiles, nq, nkv, d,
                                   self.scale, meta.pf_part_o, meta.pf_part_ml, meta.pf_combine,
                                   meta.pf_num_combine, meta.pf_num_partials,
-                                  invariant=self.invariant)
+                                  invariant=self.invariant, k_scale=k_scale, v_scale=v_scale)
         return attn
 
     def _forward_fused(self, input_ids: torch.Tensor, meta: AttnMeta, kv_caches) -> torch.Tensor:
@@ -1002,9 +1057,11 @@ class LlamaModel:
             qkv = torch.empty(t, nqkv, dtype=self.dtype, device=self.device)
             nt, dp, sp, wn = cq
             ops.pkr_gemm(residual, L.fqkv, "store", ws=ws, splits=sp, nt=nt, depth=dp, wn=wn)
+            ksc, vsc, kin, vin = self._layer_scales(li, kc)
             ops.slab_rope_kv(ws, sp, t, nqkv, qkv, meta.positions, self.cos_sin,
-                             meta.slot_mapping, kc, vc, nq, nkv, d, residual=residual, eps=eps)
-            attn = self._attention(qkv, meta, kc, vc)
+                             meta.slot_mapping, kc, vc, nq, nkv, d, residual=residual, eps=eps,
+                             k_inv=kin, v_inv=vin)
+            attn = self._attention(qkv, meta, kc, vc, ksc, vsc)
             nt, dp, sp, wn = co
             ops.pkr_gemm(attn, L.fo, "resid", residual=residual, ws=ws, tickets=tk, splits=sp,
                          nt=nt, depth=dp, wn=wn)
@@ -1043,9 +1100,11 @@ class LlamaModel:
             kc, vc = kv_caches[li]
             qkv = torch.empty(t, nqkv, dtype=self.dtype, device=self.device)
             ops.skinny_gemm(residual, L.wqkv_pk, ws=self.ws, splits=sp, nt=nt, u=u)
+            ksc, vsc, kin, vin = self._layer_scales(li, kc)
             ops.slab_rope_kv(self.ws, sp, t, nqkv, qkv, meta.positions, self.cos_sin,
-                             meta.slot_mapping, kc, vc, nq, nkv, d, residual=residual, eps=eps)
-            attn = self._attention(qkv, meta, kc, vc)
+                             meta.slot_mapping, kc, vc, nq, nkv, d, residual=residual, eps=eps,
+                             k_inv=kin, v_inv=vin)
+            attn = self._attention(qkv, meta, kc, vc, ksc, vsc)
             ops.decode_block(attn, residual, self.db_h, L.wo_pk, L.wgu_pk, L.wd_pk, self.ws,
                              self.db_xg, self.db_ctl, eps)
         idx = meta.logits_indices
@@ -1090,15 +1149,16 @@ class LlamaModel:
             else:
                 ops.fused_add_rmsnorm(x, residual, L.ln1, eps)
             kc, vc = kv_caches[li]
+            ksc, vsc, kin, vin = self._layer_scales(li, kc)
             sq, qkv = self._lin(x, L, "qkv")
             if sq:  # split-K slabs -> RoPE'd q and the paged K/V write in one kernel
                 qkv = torch.empty(t, (nq + 2 * nkv) * d, dtype=self.dtype, device=self.device)
                 ops.slab_rope_kv(self.ws, sq, t, qkv.shape[1], qkv, meta.positions, self.cos_sin,
-                                 meta.slot_mapping, kc, vc, nq, nkv, d)
+                                 meta.slot_mapping, kc, vc, nq, nkv, d, k_inv=kin, v_inv=vin)
             else:
                 ops.rope_kv_write(qkv, meta.positions, self.cos_sin, meta.slot_mapping, kc, vc,
-                                  nq, nkv, d)
-            attn = self._attention(qkv, meta, kc, vc)
+                                  nq, nkv, d, k_inv=kin, v_inv=vin)
+            attn = self._attention(qkv, meta, kc, vc, ksc, vsc)
             so, y = self._lin(attn, L, "o")
             if tps:
                 x = torch.empty(t, H, dtype=self.dtype, device=self.device) if tpf else None

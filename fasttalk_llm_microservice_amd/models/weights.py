@@ -166,6 +166,56 @@ def load_full_layer(idx: SafetensorsIndex, layer: int, dtype) -> Dict[str, torch
 
 
 # --------------------------------------------------------------------------------------
+# fp8 KV-cache scales carried by a checkpoint
+# --------------------------------------------------------------------------------------
+# Accepted per-layer tensor names (suffix after "model.layers.N."): key -> which of
+# (K, V) it sets.  vLLM's fp8-KV checkpoints use k_scale / v_scale; the legacy form is
+# one kv_scale for both.  No real fp8-KV checkpoint was at hand to check this list
+# against, so it is kept in this one table.
+KV_SCALE_NAMES = {
+    "self_attn.k_scale": ("k",),
+    "self_attn.v_scale": ("v",),
+    "self_attn.kv_scale": ("k", "v"),
+}
+
+
+def check_kv_scales(t: torch.Tensor, what: str) -> torch.Tensor:
+    """fp32 copy of a scale tensor; raises unless every value is finite and > 0."""
+    t = torch.as_tensor(t, dtype=torch.float32)
+    if not bool(torch.isfinite(t).all()) or not bool((t > 0).all()):
+        raise ValueError(f"{what}: KV scales must be finite and positive, got {t.flatten().tolist()}")
+    return t
+
+
+def load_kv_scales(cfg: ModelConfig, idx: "SafetensorsIndex"):
+    """(k, v) fp32 [num_layers, num_kv_heads] from a checkpoint's per-layer scale
+    tensors (KV_SCALE_NAMES; a scalar / one element is broadcast over the heads, or
+    [num_kv_heads]); None when the checkpoint has none.  Layers without a tensor keep
+    1.0.  A non-finite or non-positive scale raises."""
+    out = {"k": torch.ones(cfg.num_layers, cfg.num_kv_heads),
+           "v": torch.ones(cfg.num_layers, cfg.num_kv_heads)}
+    found = False
+    for li in range(cfg.num_layers):
+        for suffix, targets in KV_SCALE_NAMES.items():
+            name = f"model.layers.{li}.{suffix}"
+            if not idx.has(name):
+                continue
+            t = check_kv_scales(idx.get(name), name).flatten()
+            if t.numel() not in (1, cfg.num_kv_heads):
+                raise ValueError(f"{name}: {t.numel()} elements, expected 1 or {cfg.num_kv_heads}")
+            for which in targets:
+                out[which][li] = t   # one element broadcasts over the heads
+            found = True
+    return (out["k"], out["v"]) if found else None
+
+
+def shard_kv_scales(cfg: ModelConfig, full: torch.Tensor, rank: int, tp: int) -> torch.Tensor:
+    """[num_layers, num_kv_heads] -> this rank's kv heads [num_layers, nkv]."""
+    k0, k1 = kv_head_range(cfg, tp, rank)
+    return full[:, k0:k1].contiguous()
+
+
+# --------------------------------------------------------------------------------------
 # AWQ (W4A16) checkpoints: AutoAWQ "GEMM" tensors per projection
 # --------------------------------------------------------------------------------------
 _HF_PROJ = {"q": "self_attn.q_proj", "k": "self_attn.k_proj", "v": "self_attn.v_proj",
@@ -236,8 +286,11 @@ def save_awq_checkpoint(cfg: ModelConfig, full_layers, embed, norm, lm_head, out
 
 
 def save_hf_checkpoint(cfg: ModelConfig, full_layers, embed, norm, lm_head: Optional[torch.Tensor],
-                       out_dir: str):
-    """Write an HF-layout safetensors checkpoint (used by tests and tooling)."""
+                       out_dir: str, kv_scales: Optional[Dict[str, object]] = None):
+    """Write an HF-layout safetensors checkpoint (used by tests and tooling).
+    ``kv_scales``: fp8 KV-cache scales to store, {"k": per-layer values, "v": ...} or
+    the legacy {"kv": ...}; each per-layer value a float or a tensor of 1 or
+    num_kv_heads elements (written as self_attn.k_scale / v_scale / kv_scale)."""
     from safetensors.torch import save_file
 
     os.makedirs(out_dir, exist_ok=True)
@@ -252,6 +305,12 @@ def save_hf_checkpoint(cfg: ModelConfig, full_layers, embed, norm, lm_head: Opti
     for li, L in enumerate(full_layers):
         for k, v in L.items():
             t[f"model.layers.{li}.{inv[k]}"] = v.contiguous()
+    for key, per_layer in (kv_scales or {}).items():
+        if f"self_attn.{key}_scale" not in KV_SCALE_NAMES:
+            raise ValueError(f"kv_scales key {key!r}: k | v | kv")
+        for li, val in enumerate(per_layer):
+            t[f"model.layers.{li}.self_attn.{key}_scale"] = \
+                torch.as_tensor(val, dtype=torch.float32).clone().contiguous()
     save_file(t, os.path.join(out_dir, "model.safetensors"))
     hf = {
         "hidden_size": cfg.hidden_size, "num_hidden_layers": cfg.num_layers,

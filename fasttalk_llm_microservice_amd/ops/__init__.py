@@ -122,13 +122,30 @@ def silu_mul(gu: torch.Tensor, out: Optional[torch.Tensor] = None, interleaved: 
 # rotary + paged KV
 # ---------------------------------------------------------------------------------
 
-def rope_kv_write(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, nq, nkv, head_dim):
+def kv_scale_inv(scale: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """The reciprocal tensor the KV writers multiply by (fp32 ``1 / scale``, computed on
+    the host so kernels and reference round identically); None stays None (= 1.0)."""
+    return ref.kv_scale_inv(scale)
+
+
+def _kv_inv(scale, inv):
+    # callers on the hot path (the model) pass the reciprocals they keep; a bare scale
+    # is inverted here (one host round trip: tests and tools)
+    return inv if inv is not None else kv_scale_inv(scale)
+
+
+def rope_kv_write(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, nq, nkv, head_dim,
+                  k_scale=None, v_scale=None, k_inv=None, v_inv=None):
+    """``k_scale`` / ``v_scale``: fp32 [nkv] per-head scales of fp8 caches (stored =
+    clamp(x / scale, +-448); None = 1.0); ``k_inv`` / ``v_inv``: their reciprocals when
+    the caller keeps them."""
+    k_inv, v_inv = _kv_inv(k_scale, k_inv), _kv_inv(v_scale, v_inv)
     if qkv.is_cuda:
         native().rope_kv_write(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, nq, nkv,
-                               head_dim)
+                               head_dim, k_inv, v_inv)
     else:
         ref.rope_kv_write(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, nq, nkv,
-                          head_dim)
+                          head_dim, k_inv=k_inv, v_inv=v_inv)
 
 
 # Batch-invariant decode attention: every (sequence, kv head) is cut into pieces of
@@ -165,41 +182,48 @@ def decode_counters(batch: int, nkv: int, device) -> torch.Tensor:
 
 
 def decode_attention(out, q, k_cache, v_cache, block_tables, seq_lens, tmp_out, tmp_ml, nq, nkv,
-                     head_dim, scale, counters: Optional[torch.Tensor] = None, piece: int = 0):
+                     head_dim, scale, counters: Optional[torch.Tensor] = None, piece: int = 0,
+                     k_scale=None, v_scale=None):
     """out[b] = attention of the single new query of sequence b (q: [B, >=nq*D] rows).
     k_cache [blocks, nkv, bs, D]; v_cache [blocks, nkv, D, bs] (transposed blocks).
     ``counters`` (decode_counters): merge shared segments inside the launch instead
     of a second combine kernel.  ``piece`` > 0: batch-invariant partition (fixed
     pieces of that many tiles per sequence; needs counters and a workspace from
-    decode_workspace(piece=...))."""
+    decode_workspace(piece=...)).  ``k_scale`` / ``v_scale``: fp32 [nkv] per-head scales
+    of fp8 caches (x = stored * scale; None = 1.0)."""
     if q.is_cuda:
         native().paged_decode_attention(out, q, k_cache, v_cache, block_tables, seq_lens, tmp_out,
-                                        tmp_ml, nq, nkv, head_dim, scale, counters, piece)
+                                        tmp_ml, nq, nkv, head_dim, scale, counters, piece,
+                                        k_scale, v_scale)
         return out
     b = q.shape[0]
     qq = q[:, : nq * head_dim].reshape(b, nq, head_dim)
     qsl = torch.arange(b + 1, dtype=torch.int32)
-    o = ref.paged_attention(qq, k_cache, v_cache, block_tables, seq_lens[:b], qsl, scale)
+    o = ref.paged_attention(qq, k_cache, v_cache, block_tables, seq_lens[:b], qsl, scale,
+                            k_scale, v_scale)
     out[:b, : nq * head_dim].copy_(o.reshape(b, nq * head_dim))
     return out
 
 
 def prefill_attention(out, q, k_cache, v_cache, block_tables, seq_lens, q_start_loc, tile_info,
                       num_tiles, nq, nkv, head_dim, scale, part_o=None, part_ml=None, combine=None,
-                      num_combine: int = 0, num_partials: int = 0, invariant: bool = False):
+                      num_combine: int = 0, num_partials: int = 0, invariant: bool = False,
+                      k_scale=None, v_scale=None):
     """Varlen causal attention of the new tokens over their paged history.
     ``tile_info``: the work items of build_prefill_tiles (4 int32 each); split-KV
     items leave fp32 partials in ``part_o`` / ``part_ml`` (prefill_partials) that
     the ``combine`` list merges (csrc/kernels/attn_prefill.hip).  ``invariant``:
-    per-row rescale decisions (batch-invariant mode, with a fixed_chunk plan)."""
+    per-row rescale decisions (batch-invariant mode, with a fixed_chunk plan).
+    ``k_scale`` / ``v_scale``: as in decode_attention."""
     if q.is_cuda:
         native().prefill_attention(out, q, k_cache, v_cache, block_tables, seq_lens, q_start_loc,
                                    tile_info, num_tiles, nq, nkv, head_dim, scale, part_o, part_ml,
-                                   combine, num_combine, num_partials, invariant)
+                                   combine, num_combine, num_partials, invariant, k_scale, v_scale)
         return out
     t = q.shape[0]
     qq = q[:, : nq * head_dim].reshape(t, nq, head_dim)
-    o = ref.paged_attention(qq, k_cache, v_cache, block_tables, seq_lens, q_start_loc, scale)
+    o = ref.paged_attention(qq, k_cache, v_cache, block_tables, seq_lens, q_start_loc, scale,
+                            k_scale, v_scale)
     out[:t, : nq * head_dim].copy_(o.reshape(t, nq * head_dim))
     return out
 
@@ -465,12 +489,15 @@ def slab_store(ws, splits, rows, cols, out):
 
 
 def slab_rope_kv(ws, splits, rows, cols, q_out, positions, cos_sin, slot_mapping, k_cache,
-                 v_cache, nq, nkv, head_dim, residual=None, eps: float = 0.0):
+                 v_cache, nq, nkv, head_dim, residual=None, eps: float = 0.0,
+                 k_scale=None, v_scale=None, k_inv=None, v_inv=None):
     """Reduces the QKV split-K slabs, applies RoPE, writes q and the paged K/V.  With
     ``residual`` (fused decode layer) the slabs are scaled by the RMS of the residual
-    row first (the input-norm weight is folded into the packed QKV weight)."""
+    row first (the input-norm weight is folded into the packed QKV weight).  KV scales as
+    in rope_kv_write."""
     native().slab_rope_kv(ws, splits, rows, cols, q_out, positions, cos_sin, slot_mapping,
-                          k_cache, v_cache, nq, nkv, head_dim, residual, eps)
+                          k_cache, v_cache, nq, nkv, head_dim, residual, eps,
+                          _kv_inv(k_scale, k_inv), _kv_inv(v_scale, v_inv))
     return q_out
 
 

@@ -73,16 +73,38 @@ def apply_rope(x: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor) 
 FP8_MAX = 448.0   # float8_e4m3fn's largest finite value
 
 
-def to_cache(x: torch.Tensor, cache: torch.Tensor) -> torch.Tensor:
+def kv_scale_inv(scale: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """fp32 reciprocals of a per-head fp8 KV scale tensor, computed on the host (IEEE
+    division) so the kernels' writers and this reference multiply by the same bits."""
+    if scale is None:
+        return None
+    return (1.0 / scale.detach().to("cpu", torch.float32)).to(scale.device)
+
+
+def to_cache(x: torch.Tensor, cache: torch.Tensor, inv: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x in the cache's dtype; fp8 caches clamp to the format's range first (a plain
-    cast turns an out-of-range value into NaN, as gfx950's converter does)."""
+    cast turns an out-of-range value into NaN, as gfx950's converter does).  ``inv``
+    (fp8 caches): fp32 per-head reciprocal scales [nkv] for x [T, nkv, D]; stored =
+    clamp(x * inv, +-448) -- the clamp comes after the scaling."""
     if cache.dtype == torch.float8_e4m3fn:
-        return x.float().clamp(-FP8_MAX, FP8_MAX).to(cache.dtype)
+        xf = x.float()
+        if inv is not None:
+            xf = xf * inv.float().view(1, -1, 1)
+        return xf.clamp(-FP8_MAX, FP8_MAX).to(cache.dtype)
+    if inv is not None:
+        raise ValueError("KV scales are given only with float8_e4m3fn caches")
     return x.to(cache.dtype)
 
 
-def rope_kv_write(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, nq, nkv, head_dim):
-    """In place: rotate q inside ``qkv``; write rotated k and v into the paged caches."""
+def rope_kv_write(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, nq, nkv, head_dim,
+                  k_scale=None, v_scale=None, k_inv=None, v_inv=None):
+    """In place: rotate q inside ``qkv``; write rotated k and v into the paged caches.
+    ``k_scale`` / ``v_scale``: per-head fp8 scales [nkv] (stored = x / scale); their
+    reciprocals may be passed ready-made as ``k_inv`` / ``v_inv``."""
+    if k_inv is None:
+        k_inv = kv_scale_inv(k_scale)
+    if v_inv is None:
+        v_inv = kv_scale_inv(v_scale)
     t = qkv.shape[0]
     if t == 0:
         return
@@ -98,8 +120,8 @@ def rope_kv_write(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, nq, n
         bs = k_cache.shape[2]
         s = slots[keep]
         blk, off = s // bs, s % bs
-        k_cache[blk, :, off, :] = to_cache(kr[keep], k_cache)
-        v_cache[blk, :, :, off] = to_cache(v[keep], v_cache)   # V blocks transposed: [blocks, nkv, D, bs]
+        k_cache[blk, :, off, :] = to_cache(kr[keep], k_cache, k_inv)
+        v_cache[blk, :, :, off] = to_cache(v[keep], v_cache, v_inv)   # V blocks transposed: [blocks, nkv, D, bs]
 
 
 def _gather_kv(cache, table_row, length, transposed: bool = False):
@@ -115,13 +137,15 @@ def _gather_kv(cache, table_row, length, transposed: bool = False):
 
 
 def paged_attention(q: torch.Tensor, k_cache, v_cache, block_tables, seq_lens, q_start_loc,
-                    scale: float) -> torch.Tensor:
+                    scale: float, k_scale=None, v_scale=None) -> torch.Tensor:
     """Causal varlen attention over the paged cache (K blocks [nkv, bs, D], V
     blocks transposed [nkv, D, bs]).
 
     q: [T, nq, D] (new tokens of every sequence, packed by q_start_loc)
     Each sequence b attends to kv positions [0, seq_lens[b]); its new tokens
     sit at the end (positions seq_len - q_len ...).  Returns [T, nq, D].
+    ``k_scale`` / ``v_scale``: per-head fp8 scales [nkv]; the cache is dequantised as
+    stored * scale.
     """
     t, nq, d = q.shape
     out = torch.empty_like(q)
@@ -136,6 +160,10 @@ def paged_attention(q: torch.Tensor, k_cache, v_cache, block_tables, seq_lens, q
         L = sl[b]
         k = _gather_kv(k_cache, block_tables[b], L).float()  # [L, nkv, D]
         v = _gather_kv(v_cache, block_tables[b], L, transposed=True).float()
+        if k_scale is not None:
+            k = k * k_scale.float().view(1, -1, 1)
+        if v_scale is not None:
+            v = v * v_scale.float().view(1, -1, 1)
         qq = q[q0:q1].float()  # [ql, nq, D]
         ql = q1 - q0
         k = k.repeat_interleave(g, dim=1)
