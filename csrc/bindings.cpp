@@ -82,6 +82,9 @@ int ft_skinny_gemm_xr(const void* x, int x_stride, int M, const void* w, int N, 
                       hipStream_t stream);
 int ft_packed_gemm(const void* x, int x_stride, int M, const void* wpk, int N, int K, int splits,
                    int epi, int cfg, void* out, int out_stride, float* ws, hipStream_t stream);
+int ft_w4_packed_gemm(const void* x, int x_stride, int M, const uint32_t* wq, const void* sz, int N,
+                      int K, int splits, int epi, int cfg, void* out, int out_stride, float* ws,
+                      hipStream_t stream);
 int ft_pkr_gemm(const void* x, int x_stride, int M, const void* wpk, int N, int K, float* ws,
                 void* out, int out_stride, void* residual, int res_stride, int* tickets,
                 int splits, int nt, int depth, int epi, int norm, int wn, float eps,
@@ -485,6 +488,46 @@ void w4_gemm(at::Tensor x, at::Tensor wq, at::Tensor sz, int64_t N, c10::optiona
                       reinterpret_cast<const uint32_t*>(wq.data_ptr<int>()), sz.data_ptr(), (int)N,
                       K, wsp, op, ostride, (int)splits, (int)nt, cur_stream()),
            "w4_gemm");
+}
+
+// W4A16 GEMM for any row count on the int4 image (csrc/kernels/w4_packed_gemm.hip).
+// epi: 0 bf16 out [M, N] (one split), 1 fp32 slabs ws [splits, M, N], 2 SiLU-mul out
+// [M, N/2] (16-row interleaved gate/up image, one split).
+void w4_packed_gemm(at::Tensor x, at::Tensor wq, at::Tensor sz, int64_t N,
+                    c10::optional<at::Tensor> out, c10::optional<at::Tensor> ws, int64_t splits,
+                    int64_t epi, int64_t cfg) {
+  check_bf16(x, "x");
+  check_rows(x, "x");
+  const int M = (int)x.size(0), K = (int)x.size(1);
+  check_w4(wq, sz, N, K);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && x.stride(0) % 8 == 0,
+              "x rows must be 16-B aligned");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "w4_packed_gemm: epi");
+  TORCH_CHECK(splits >= 1 && K % (128 * splits) == 0, "w4_packed_gemm: K % (128 * splits)");
+  TORCH_CHECK(epi == 1 || splits == 1, "w4_packed_gemm: splits > 1 leaves slabs (epi 1)");
+  TORCH_CHECK(epi != 2 || N % 32 == 0, "w4_packed_gemm: the SiLU epilogue needs N % 32 == 0");
+  TORCH_CHECK(cfg >= 0 && cfg <= 2, "w4_packed_gemm: cfg");
+  float* wsp = nullptr;
+  void* op = nullptr;
+  int ostride = 0;
+  if (epi == 1) {
+    TORCH_CHECK(ws.has_value(), "slabs need a workspace");
+    check_ws(*ws, (int64_t)splits * M * N);
+    wsp = ws->data_ptr<float>();
+  } else {
+    TORCH_CHECK(out.has_value(), "needs out");
+    check_bf16(*out, "out");
+    const int64_t cols = epi == 2 ? N / 2 : N;
+    TORCH_CHECK(out->dim() == 2 && out->stride(1) == 1 && out->size(0) >= M && out->size(1) >= cols,
+                "out shape");
+    op = out->data_ptr();
+    ostride = (int)out->stride(0);
+  }
+  check_rc(ft_w4_packed_gemm(x.data_ptr(), (int)x.stride(0), M,
+                             reinterpret_cast<const uint32_t*>(wq.data_ptr<int>()), sz.data_ptr(),
+                             (int)N, K, (int)splits, (int)epi, (int)cfg, op, ostride, wsp,
+                             cur_stream()),
+           "w4_packed_gemm");
 }
 
 void w4_dequant(at::Tensor wq, at::Tensor sz, at::Tensor out) {
@@ -971,6 +1014,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out") = py::none(), py::arg("ws") = py::none(), py::arg("splits") = 1,
         py::arg("nt") = 1, py::arg("xr") = false, py::arg("silu") = false);
   m.def("w4_dequant", &w4_dequant);
+  m.def("w4_packed_gemm", &w4_packed_gemm);
   m.def("skinny_gemm_xr", &skinny_gemm_xr, py::arg("x"), py::arg("w"), py::arg("out") = py::none(),
         py::arg("ws") = py::none(), py::arg("splits") = 1, py::arg("nt") = 2, py::arg("epi") = 0,
         py::arg("nw") = 4);

@@ -30,6 +30,9 @@ def _bool(v: str) -> bool:
     return str(v).lower() in ("1", "true", "yes", "on")
 
 
+W4_PREFILL_MODES = ("auto", "image", "scratch", "int4")
+
+
 @dataclasses.dataclass
 class EngineConfig:
     model: str = "llama3.1-8b"
@@ -76,9 +79,23 @@ class EngineConfig:
     # "calibrate": one prefill of a built-in chat prompt at start-up | a .json path
     # ({"k": [[nkv floats] per layer], "v": ...}; LLMEngine.save_kv_scales writes one)
     kv_scales: str = "auto"
+    # W4A16 above 64 rows (prefill chunks, mixed steps): "auto" (FT_W4_PREFILL_IMAGE
+    # decides: a resident dequantized bf16 image when memory allows, "0" the per-step
+    # scratch, "int4" as below) | "image" | "scratch" | "int4": the W4 GEMM straight on
+    # the int4 image (w4_packed_gemm.hip), no bf16 copy of any projection
+    w4_prefill: str = "auto"
 
     def __post_init__(self):
         self.check_kv_scales()
+        self.check_w4_prefill()
+
+    def check_w4_prefill(self) -> str:
+        """auto | image | scratch | int4 (normalised in place); ValueError otherwise."""
+        v = (self.w4_prefill or "auto").strip().lower()
+        if v not in W4_PREFILL_MODES:
+            raise ValueError(f"w4_prefill {self.w4_prefill!r}: " + " | ".join(W4_PREFILL_MODES))
+        self.w4_prefill = v
+        return v
 
     def check_kv_scales(self) -> str:
         """auto | one | calibrate | file; ValueError for anything else, and for a value
@@ -162,10 +179,12 @@ class EngineConfig:
             batch_invariant=_env(["ENGINE_BATCH_INVARIANT", "VLLM_BATCH_INVARIANT"], False, _bool),
             kv_cache_dtype=_env(["ENGINE_KV_CACHE_DTYPE", "VLLM_KV_CACHE_DTYPE"], "auto"),
             kv_scales=_env(["ENGINE_KV_SCALES"], "auto"),
+            w4_prefill=_env(["ENGINE_W4_PREFILL"], "auto"),
         )
         for k, v in overrides.items():
             setattr(c, k, v)
         c.check_kv_scales()
+        c.check_w4_prefill()
         if c.separate_process is None:
             # a TP group runs in its own process by default: when a worker dies the
             # supervisor (parallel/dp_router.py) can tear the group down and respawn it

@@ -874,6 +874,7 @@ class LLMEngine:
             "kv_usage": self.kv_usage(),
             "kv_cache_dtype": self.cfg.kv_cache_dtype,
             "kv_scales": dict(getattr(self.runner, "kv_scale_info", None) or {"source": "one"}),
+            **dict(getattr(self.runner, "weights_info", None) or {}),
             "prefix_cache_hit_rate": (self.bm.hits / self.bm.queries) if self.bm.queries else 0.0,
             "preemptions": self.scheduler.num_preemptions,
             "guided_capped_steps": self.scheduler.guided_capped,

@@ -202,14 +202,24 @@ class ModelRunner:
 
         t0 = time.time()
         self.model = LlamaModel(model_cfg, self.device, self.dtype, comm, self.max_model_len,
-                                quantization=cfg.quantization)
+                                quantization=cfg.quantization,
+                                w4_prefill=getattr(cfg, "w4_prefill", "auto"))
         if cfg.weights and cfg.weights != "random":
             self.model.load_checkpoint(cfg.weights)
         else:
             self.model.init_random(seed=cfg.seed)
         if self.is_gpu:
             torch.cuda.synchronize(self.device)
-        log.info("weights ready in %.1fs", time.time() - t0)
+        # /stats: what the weights occupy, and (W4 engines on the GPU) how their
+        # projections run above 64 rows
+        self.weights_info = {
+            "weights_resident_gb": round(self.model.weights_resident_bytes() / 1e9, 6)}
+        w4_mode = self.model.w4_prefill_mode()
+        if w4_mode is not None:
+            self.weights_info["w4_prefill"] = w4_mode
+        log.info("weights ready in %.1fs: %.3f GB resident%s", time.time() - t0,
+                 self.weights_info["weights_resident_gb"],
+                 f", W4 above 64 rows: {w4_mode}" if w4_mode else "")
 
         # batch-invariant numerics (cfg.batch_invariant): rows of a step up to the token
         # budget plus a decode row per sequence

@@ -179,6 +179,35 @@ def pg_cfg(proj: str, rows: int, k: int) -> Tuple[int, int]:
     return cfg, sp
 
 
+# W4A16 above W4_ROWS rows in w4_prefill="int4" mode: w4_packed_gemm.hip on the int4
+# image, (row limit, tile cfg, split-K) per projection.  Tiles: cfg 0 = 128 x 256,
+# 1 = 256 x 128, 2 = 128 x 128; the row limits follow the tile heights (a step of
+# 129-256 rows is one 256-row tile, 257-384 rows three 128-row tiles).  Entries from
+# the cold-weight sweep of bench/w4pg_probe.py --sweep on MI355X at 145 / 300 / 512 /
+# 1024 rows (profiles/w4_prefill_int4_r07.log; us, packed_gemm on the dequantized
+# image in brackets): qkv 33 / 49 / 52 / 81 [31 / 42 / 51 / 77], o 25 / 34 / 37 / 54
+# [26 / 29 / 37 / 53], gate_up + SiLU 84 / 141 / 155 / 304 [89 / 114 / 132 / 219],
+# down 46 / 81 / 87 / 148 [56 / 71 / 87 / 132].  <= 128 rows keep PG_PLAN's splits.
+W4PG_PLAN = {
+    "qkv": ((128, 0, 8), (256, 1, 4), (384, 0, 2), (512, 2, 1), (1 << 30, 0, 1)),
+    "o": ((128, 2, 8), (256, 1, 8), (384, 0, 4), (512, 2, 2), (2047, 2, 1), (1 << 30, 0, 1)),
+    "gu": ((128, 0, 2), (256, 1, 1), (384, 0, 2), (1 << 30, 0, 1)),
+    "down": ((128, 0, 16), (256, 1, 8), (384, 0, 4), (512, 0, 4), (2047, 0, 2), (1 << 30, 0, 1)),
+}
+
+
+def w4pg_cfg(proj: str, rows: int, n: int, k: int, ws_elems: Optional[int] = None) -> Tuple[int, int]:
+    """(tile cfg, splits) of a W4 GEMM above W4_ROWS rows: the plan's splits halved
+    until they divide K into whole 128-wide groups and (``ws_elems`` given) the fp32
+    slabs [splits, rows, n] fit the workspace."""
+    for lim, cfg, sp in W4PG_PLAN[proj]:
+        if rows <= lim:
+            break
+    while sp > 1 and (k % (128 * sp) or (ws_elems is not None and sp * rows * n > ws_elems)):
+        sp //= 2
+    return cfg, sp
+
+
 def _cfg_fits(c, n: int, k: int) -> bool:
     nt, u, sp = c
     kq = {-4: 512, -5: 512 if nt == 2 else 256, -6: 512,
@@ -401,7 +430,8 @@ def _packable(n: int, k: int, proj: str) -> bool:
 
 class LlamaModel:
     def __init__(self, cfg: ModelConfig, device: torch.device, dtype: torch.dtype = torch.bfloat16,
-                 comm: TPComm = SINGLE, max_model_len: int = 8192, quantization: Optional[str] = None):
+                 comm: TPComm = SINGLE, max_model_len: int = 8192, quantization: Optional[str] = None,
+                 w4_prefill: str = "auto"):
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = dtype
@@ -431,6 +461,15 @@ class LlamaModel:
         self.quant = (quantization or "").lower() or None
         if self.quant not in (None, "awq", "w4"):
             raise ValueError(f"unsupported quantization {quantization!r} (awq | w4)")
+        # W4 above W4_ROWS rows: auto (FT_W4_PREFILL_IMAGE decides) | image | scratch |
+        # int4 (w4_packed_gemm.hip on the int4 image; no bf16 copy, no scratch)
+        self.w4_prefill = (w4_prefill or "auto").lower()
+        if self.w4_prefill not in ("auto", "image", "scratch", "int4"):
+            raise ValueError(f"w4_prefill {w4_prefill!r}: auto | image | scratch | int4")
+        if self.w4_prefill == "auto" and \
+                os.environ.get("FT_W4_PREFILL_IMAGE", "auto").lower() == "int4":
+            self.w4_prefill = "int4"
+        self.w4_int4 = False      # set by _prepare_w4_prefill (GPU, W4 layers, int4 mode)
         self._w4_scratch: Optional[torch.Tensor] = None
         self.w4_gu_il = False     # W4 gate_up image interleaved in 16-row groups
         self.fused = False
@@ -624,9 +663,18 @@ class LlamaModel:
         after the bf16 image -- 8B: 14 GB of 288; 70B at TP=1: 140 GB next to 35 GB of
         int4, 50 sessions 1,006 -> 1,386 tok/s, p50 TTFT 449 -> 165 ms,
         profiles/bench_70b_awq_image_s50_r06.log), 1, 0 (int4 only: the least memory,
-        prefill-size steps dequantize per projection)."""
+        prefill-size steps dequantize per projection), int4 (no image and no scratch:
+        _lin runs w4_packed_gemm.hip on the int4 image, _w4_pg).  The model's
+        ``w4_prefill`` (EngineConfig.w4_prefill: image | scratch | int4) overrides it."""
         mode = os.environ.get("FT_W4_PREFILL_IMAGE", "auto")
-        if self.quant is None or mode == "0" or self.device.type != "cuda" or not self.layers:
+        if self.w4_prefill != "auto":   # EngineConfig.w4_prefill overrides the variable
+            mode = {"image": "1", "scratch": "0"}.get(self.w4_prefill, self.w4_prefill)
+        if self.quant is None or self.device.type != "cuda" or not self.layers:
+            return
+        if mode == "int4":   # nothing to build: _lin runs the W4 GEMM on the int4 image
+            self.w4_int4 = any(L.q4 for L in self.layers)
+            return
+        if mode == "0":
             return
         qs = [(L, p, L.q4[p]) for L in self.layers for p in _ATTR if L.q4 and p in L.q4]
         if not qs:
@@ -697,6 +745,10 @@ class LlamaModel:
                 for nt, sp, xr in W4_PLAN[proj].values())
             if self.w4_slab[proj]:
                 need = max(need, max(sp * b * q.n for b, (_, sp, _) in W4_PLAN[proj].items()))
+        if self.w4_int4:   # the W4 GEMM's split-K slabs above W4_ROWS rows
+            for proj, q in (L0.q4 or {}).items():
+                need = max(need, max((sp * min(lim, PG_MAX_SLAB_ROWS) * q.n
+                                      for lim, _, sp in W4PG_PLAN[proj] if sp > 1), default=0))
         self.ws = torch.empty(need, dtype=torch.float32, device=self.device)
         # in-launch split-K tickets (fused ring layer): zeroed,
         # every launch leaves them zeroed
@@ -897,6 +949,8 @@ class LlamaModel:
                     return sp, None
                 y = Q.w4_gemm(x, q, nt=nt, xr=xr)
             else:
+                if self.w4_int4:   # the W4 GEMM on the int4 image itself
+                    return self._w4_pg(x, q, proj)
                 # the dequantized prefill image (_prepare_w4_prefill), or this
                 # projection dequantized and packed into a scratch when it is off
                 wp = getattr(L, _ATTR[proj] + "_pk")
@@ -913,6 +967,64 @@ class LlamaModel:
             y = F.linear(x, getattr(L, attr))
             return 0, (ops.silu_mul(y) if proj == "gu" else y)
         return self._packed(x, wp, proj)
+
+    def _w4_pg(self, x: torch.Tensor, q: "Q.W4Weight", proj: str) -> Tuple[int, Optional[torch.Tensor]]:
+        """y = x dequant(W)^T above W4_ROWS rows on the int4 image (w4_packed_gemm.hip),
+        the packed_gemm tail of _packed: split-K slabs left for the fused consumer when
+        it can take them, else reduced by slab_store (TP / odd hidden); gate_up through
+        the SiLU epilogue when the image is interleaved."""
+        rows = x.shape[0]
+        gu = proj == "gu"
+        cfg, sp = w4pg_cfg(proj, rows, q.n, q.k, self.ws.numel() if self.ws is not None else 0)
+        if gu and not self.w4_gu_il:   # slab_silu pairs an interleaved image's columns
+            sp = 1
+        if sp > 1:
+            Q.w4_packed_gemm(x, q, ws=self.ws, splits=sp, epi="slab", cfg=cfg)
+            if self._slab_ok(proj, rows):
+                return sp, None
+            y = torch.empty(rows, q.n, dtype=x.dtype, device=x.device)  # TP / odd hidden
+            ops.slab_store(self.ws, sp, rows, q.n, y)
+            return 0, y
+        if gu:
+            if self.w4_gu_il:
+                return 0, Q.w4_packed_gemm(x, q, epi="silu", cfg=cfg)
+            return 0, ops.silu_mul(Q.w4_packed_gemm(x, q, cfg=cfg), interleaved=False)
+        return 0, Q.w4_packed_gemm(x, q, cfg=cfg)
+
+    def w4_prefill_mode(self) -> Optional[str]:
+        """How W4 projections run above W4_ROWS rows: int4 | image | scratch; None for a
+        bf16 model and on the CPU backend (dequantized weights)."""
+        if self.quant is None or self.device.type != "cuda" or \
+                not any(L.q4 for L in self.layers):
+            return None
+        if self.w4_int4:
+            return "int4"
+        pk = [getattr(L, _ATTR[p] + "_pk") is not None for L in self.layers for p in (L.q4 or {})]
+        return "image" if pk and all(pk) else "scratch"
+
+    def weights_resident_bytes(self) -> int:
+        """Bytes of weights this model holds: int4 images, every bf16 / packed tensor
+        of the layers (norms included), embedding, LM head and final norm.  Tensors
+        that share storage (a tied LM head) count once."""
+        seen, total = set(), 0
+
+        def add(t):
+            nonlocal total
+            if t is None or t.untyped_storage().data_ptr() in seen:
+                return
+            seen.add(t.untyped_storage().data_ptr())
+            total += t.numel() * t.element_size()
+
+        for L in self.layers:
+            for q in (L.q4 or {}).values():
+                total += q.nbytes()
+            for f in dataclasses.fields(L):
+                v = getattr(L, f.name)
+                if isinstance(v, torch.Tensor):
+                    add(v)
+        for t in (self.embed, self.lm_head, self.lm_head_pk, self.norm):
+            add(t)
+        return total
 
     def _packed(self, x: torch.Tensor, wp: torch.Tensor, proj: str) -> Tuple[int, Optional[torch.Tensor]]:
         """y = x W^T on the packed image: the decode kernels up to PACKED_ROWS rows

@@ -102,6 +102,7 @@ KERNEL_FLAGS = {
     "attn_prefill": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"],
     # W4: the per-group scale / zero correction reads every MFMA result on the VALU
     "w4a16": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    "w4_packed_gemm": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 }
 
 

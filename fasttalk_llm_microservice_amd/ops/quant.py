@@ -170,3 +170,47 @@ def w4_gemm(x: torch.Tensor, w: W4Weight, out=None, ws=None, splits: int = 1, nt
         out = torch.empty(x.shape[0], w.n // 2 if silu else w.n, dtype=x.dtype, device=x.device)
     native().w4_gemm(x, w.wq, w.sz, w.n, out, ws, splits, nt, int(xr), silu)
     return out if ws is None else ws
+
+
+_W4PG_EPI = {"store": 0, "slab": 1, "silu": 2}
+
+
+def w4_packed_gemm(x: torch.Tensor, w: W4Weight, out=None, ws=None, splits: int = 1,
+                   epi: str = "store", cfg: int = 0):
+    """y = x dequant(w)^T for any row count on the int4 image
+    (csrc/kernels/w4_packed_gemm.hip), with the decode kernels' numerics: exact
+    (q - z) * s weights, fp32 accumulation.  epi "store": bf16 [M, N]; "slab": fp32
+    slabs [splits, M, N] in ``ws`` (any split count); "silu": silu(gate) * up of an
+    image interleaved in 16-row groups -> [M, N / 2].  cfg: 0 = 128 x 256 tile,
+    1 = 256 x 128, 2 = 128 x 128.  Returns ``ws`` for slabs, else ``out``."""
+    code = _W4PG_EPI[epi]
+    if splits < 1 or w.k % (GROUP * splits):
+        raise ValueError(f"w4_packed_gemm: K {w.k} is not a multiple of 128 * splits ({splits})")
+    if code != 1 and splits != 1:
+        raise ValueError("w4_packed_gemm: splits > 1 leaves slabs (epi='slab')")
+    if code == 2 and w.n % 32:
+        raise ValueError(f"w4_packed_gemm: the SiLU epilogue needs N % 32 == 0 (N = {w.n})")
+    if code == 1 and ws is None:
+        raise ValueError("w4_packed_gemm: slabs need a workspace")
+    if not x.is_cuda:
+        m = x.shape[0]
+        y = x.float() @ w4_dequant(w, dtype=torch.float32).t()
+        if code == 1:   # the whole product in slab 0
+            slabs = ws.view(-1)[:splits * m * w.n].view(splits, m, w.n)
+            slabs.zero_()
+            slabs[0].copy_(y)
+            return ws
+        if code == 2:
+            g, u = y.view(m, -1, 2, 16).unbind(2)
+            y = (torch.nn.functional.silu(g) * u).reshape(m, -1)
+        y = y.to(x.dtype)
+        if out is not None:
+            out[:m, :y.shape[1]].copy_(y)
+            return out
+        return y
+    from . import native
+
+    if code != 1 and out is None:
+        out = torch.empty(x.shape[0], w.n // 2 if code == 2 else w.n, dtype=x.dtype, device=x.device)
+    native().w4_packed_gemm(x, w.wq, w.sz, w.n, out, ws, splits, code, cfg)
+    return ws if code == 1 else out
