@@ -213,7 +213,8 @@ class VoiceAgent:
                               temperature: Optional[float] = None, max_tokens: Optional[int] = None,
                               top_p: Optional[float] = None, top_k: Optional[int] = None,
                               stop=None, seed: Optional[int] = None, tool_choice: Optional[str] = None,
-                              ignore_eos: bool = False, min_tokens: int = 0
+                              ignore_eos: bool = False, min_tokens: int = 0,
+                              penalties: Optional[Dict[str, Any]] = None
                               ) -> AsyncGenerator[AgentEvent, None]:
         temp = self.config.temperature if temperature is None else temperature
         mt = self.config.max_tokens if max_tokens is None else max_tokens
@@ -221,7 +222,8 @@ class VoiceAgent:
         backend = self._get_backend()
         if not self.is_native:
             async for ev in self._remote_events(backend, user_message, context, temp, mt, tp, top_k,
-                                                stop, seed, tool_choice, ignore_eos, min_tokens):
+                                                stop, seed, tool_choice, ignore_eos, min_tokens,
+                                                penalties):
                 yield ev
             return
 
@@ -263,7 +265,8 @@ class VoiceAgent:
                     prefix_session=sid, assistant_prefix=head, tools=schemas or None, guided=guided,
                     seed=seed, guided_lazy=lazy,
                     ignore_eos=ignore_eos and (guided is None or lazy), min_tokens=min_tokens,
-                    priority=self.config.tool_round_priority if rnd > 0 else 0):
+                    priority=self.config.tool_round_priority if rnd > 0 else 0,
+                    penalties=penalties):
                 if out.finished:
                     finish = out.finish_reason
                 n = len(out.token_ids)
@@ -314,8 +317,8 @@ class VoiceAgent:
         yield AgentEvent(finish_reason="length")
 
     async def _remote_events(self, backend, user_message: str, context: ConversationContext,
-                             temp, mt, tp, top_k, stop, seed, tool_choice, ignore_eos, min_tokens
-                             ) -> AsyncGenerator[AgentEvent, None]:
+                             temp, mt, tp, top_k, stop, seed, tool_choice, ignore_eos, min_tokens,
+                             penalties=None) -> AsyncGenerator[AgentEvent, None]:
         """The reference's default path (PydanticAI over the vLLM OpenAI API,
         ``/root/reference/app/agents/voice_agent.py:141-164,219-229``): the flattened
         history prompt, the tool schemas sent with every request (the server parses
@@ -330,6 +333,9 @@ class VoiceAgent:
         force = self._wants_tool(user_message, tool_choice)
         extra = {"top_k": top_k, "seed": seed, "ignore_eos": True if ignore_eos else None,
                  "min_tokens": min_tokens or None}
+        from app.core.vllm_handler import remote_penalties
+
+        extra.update(remote_penalties(penalties))   # every round of the tool loop
         chat = getattr(backend, "stream_chat_async", None)
         for rnd in range(self.config.max_tool_rounds + 1):
             offer = bool(schemas) and rnd < self.config.max_tool_rounds and chat is not None
@@ -344,7 +350,7 @@ class VoiceAgent:
             if chat is None:   # a backend without the chat/tool API: text only
                 async for text in backend.generate_stream_async(
                         messages=messages, temperature=temp, max_tokens=mt, top_p=tp,
-                        request_id=context.session_id):
+                        request_id=context.session_id, penalties=penalties):
                     yield AgentEvent(text=text, num_tokens=1)
                 yield AgentEvent(finish_reason="stop")
                 return

@@ -137,6 +137,11 @@ class NativeHandler:
         self.max_model_len = inner.max_model_len
         self.model = model or getattr(inner.model_cfg, "name", "native")
         self.default_max_tokens = default_max_tokens
+        # DEFAULT_REPETITION_PENALTY / _PRESENCE_ / _FREQUENCY_: what a request leaves out
+        self.default_penalties: Dict[str, Any] = {
+            k: float(getattr(config, "default_" + k))
+            for k in ("repetition_penalty", "presence_penalty", "frequency_penalty")
+            if getattr(config, "default_" + k, None) is not None}
         self._active: Dict[str, str] = {}      # session/request key -> engine request id
         self._sessions: Dict[str, _SessionTokens] = {}
         self._lock = threading.Lock()
@@ -322,8 +327,15 @@ class NativeHandler:
 
     # ------------------------------------------------------------------ generation
     def _params(self, temperature, max_tokens, top_p, top_k=None, stop=None, seed=None,
-                guided=None, ignore_eos=False, min_tokens=0, guided_lazy=False, priority=0):
+                guided=None, ignore_eos=False, min_tokens=0, guided_lazy=False, priority=0,
+                penalties=None):
+        """``penalties``: repetition_penalty / presence_penalty / frequency_penalty /
+        logit_bias (engine.sampling_params.pick_penalties); the service defaults
+        (DEFAULT_REPETITION_PENALTY ...) fill in what a request leaves out."""
         from fasttalk_llm_microservice_amd.engine.sampling_params import SamplingParams
+
+        pen = {k: v for k, v in self.default_penalties.items()}
+        pen.update({k: v for k, v in (penalties or {}).items() if v is not None})
 
         return SamplingParams(
             temperature=0.7 if temperature is None else float(temperature),
@@ -331,7 +343,7 @@ class NativeHandler:
             top_k=0 if top_k in (None, -1) else int(top_k),
             max_tokens=int(max_tokens or self.default_max_tokens),
             stop=stop, seed=seed, guided=guided, ignore_eos=ignore_eos, min_tokens=min_tokens,
-            guided_lazy=bool(guided_lazy and guided is not None), priority=int(priority))
+            guided_lazy=bool(guided_lazy and guided is not None), priority=int(priority), **pen)
 
     async def stream_events(self, messages: List[Dict[str, Any]], temperature: Optional[float] = None,
                             max_tokens: Optional[int] = None, top_p: Optional[float] = None,
@@ -341,7 +353,8 @@ class NativeHandler:
                             seed: Optional[int] = None, ignore_eos: bool = False,
                             min_tokens: int = 0, prefix_session: Optional[str] = None,
                             assistant_prefix: str = "", guided_lazy: bool = False,
-                            priority: int = 0) -> AsyncIterator[Any]:
+                            priority: int = 0, penalties: Optional[Dict[str, Any]] = None
+                            ) -> AsyncIterator[Any]:
         """``prefix_session`` (with ``session_id=None``): build the prompt on that
         session's token stream without making this request the session's turn.
         ``assistant_prefix``: text the assistant turn starts with (written into the
@@ -349,7 +362,7 @@ class NativeHandler:
         prefills ahead of waiting prompts of lower priority."""
         mt = int(max_tokens or self.default_max_tokens)
         params = self._params(temperature, mt, top_p, top_k, stop, seed, guided, ignore_eos,
-                              min_tokens, guided_lazy, priority)
+                              min_tokens, guided_lazy, priority, penalties)
         if prompt_ids is None:
             if session_id is None and prefix_session is not None:
                 prompt_ids = self.build_prompt(messages, mt, prefix_session, tools, remember=False)
@@ -384,20 +397,22 @@ class NativeHandler:
                                     max_tokens: Optional[int] = None, top_p: Optional[float] = None,
                                     stop: Optional[List[str]] = None, tools=None,
                                     request_id: Optional[str] = None, top_k: Optional[int] = None,
-                                    session_id: Optional[str] = None) -> AsyncIterator[str]:
+                                    session_id: Optional[str] = None,
+                                    penalties: Optional[Dict[str, Any]] = None) -> AsyncIterator[str]:
         async for out in self.stream_events(messages, temperature, max_tokens, top_p, top_k, stop,
-                                            request_id, session_id, tools=tools):
+                                            request_id, session_id, tools=tools, penalties=penalties):
             if out.text:
                 yield out.text
 
     def generate_stream(self, messages: List[Dict[str, str]], temperature: Optional[float] = None,
                         max_tokens: Optional[int] = None, top_p: Optional[float] = None,
                         stop: Optional[List[str]] = None, tools=None,
-                        request_id: Optional[str] = None, top_k: Optional[int] = None) -> Iterator[str]:
+                        request_id: Optional[str] = None, top_k: Optional[int] = None,
+                        penalties: Optional[Dict[str, Any]] = None) -> Iterator[str]:
         """Synchronous iterator (drives a private event loop)."""
         loop = asyncio.new_event_loop()
         agen = self.generate_stream_async(messages, temperature, max_tokens, top_p, stop, tools,
-                                          request_id, top_k)
+                                          request_id, top_k, penalties=penalties)
         try:
             while True:
                 try:

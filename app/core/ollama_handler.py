@@ -55,10 +55,19 @@ class OllamaHandler:
     def generate_stream(self, messages: List[Dict[str, str]], temperature: Optional[float] = None,
                         max_tokens: Optional[int] = None, top_p: Optional[float] = None,
                         top_k: Optional[int] = None, stop: Optional[List[str]] = None,
-                        request_id: Optional[str] = None) -> Generator[str, None, None]:
+                        request_id: Optional[str] = None,
+                        penalties: Optional[Dict[str, Any]] = None) -> Generator[str, None, None]:
         req_id = request_id or f"ollama-{uuid.uuid4()}"
         options = {k: v for k, v in (("temperature", temperature), ("num_predict", max_tokens),
                                      ("top_p", top_p), ("top_k", top_k), ("stop", stop)) if v is not None}
+        # Ollama's options know repeat_penalty / presence_penalty / frequency_penalty (no
+        # logit_bias); values at their neutral defaults are left out
+        pen = penalties or {}
+        for name, key, neutral in (("repeat_penalty", "repetition_penalty", 1.0),
+                                   ("presence_penalty", "presence_penalty", 0.0),
+                                   ("frequency_penalty", "frequency_penalty", 0.0)):
+            if pen.get(key) is not None and float(pen[key]) != neutral:
+                options[name] = float(pen[key])
         payload = {"model": self.model, "messages": messages, "stream": True, "options": options,
                    "keep_alive": self.keep_alive}
         resp = None

@@ -57,6 +57,14 @@ def register_openai_routes(app, handler) -> None:
                   top_k=body.get("top_k"), stop=stop, tools=tools, guided=guided,
                   seed=body.get("seed"), ignore_eos=bool(body.get("ignore_eos", False)),
                   min_tokens=int(body.get("min_tokens") or 0))
+        # presence_penalty / frequency_penalty / logit_bias, and vLLM's repetition_penalty
+        from fasttalk_llm_microservice_amd.engine.sampling_params import pick_penalties
+
+        try:
+            kw["penalties"] = pick_penalties(body) or None
+        except (ValueError, TypeError) as e:
+            return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}},
+                                status_code=400)
         rid = f"chatcmpl-{uuid.uuid4().hex[:24]}"
         created = int(time.time())
         model = body.get("model") or handler.model

@@ -22,6 +22,21 @@ from app.utils.error_handler import ErrorCategory, ErrorSeverity, LLMServiceErro
 logger = logging.getLogger(__name__)
 
 
+def remote_penalties(penalties: Optional[Dict[str, Any]]) -> Dict[str, Any]:
+    """OpenAI / vLLM request-body fields of the sampler penalties a session set:
+    presence_penalty, frequency_penalty, logit_bias and vLLM's repetition_penalty;
+    values at their neutral defaults are left out."""
+    pen = penalties or {}
+    out: Dict[str, Any] = {}
+    for key, neutral in (("repetition_penalty", 1.0), ("presence_penalty", 0.0),
+                         ("frequency_penalty", 0.0)):
+        if pen.get(key) is not None and float(pen[key]) != neutral:
+            out[key] = float(pen[key])
+    if pen.get("logit_bias"):
+        out["logit_bias"] = {str(k): v for k, v in pen["logit_bias"].items()}
+    return out
+
+
 def _sse_payloads(lines):
     for line in lines:
         if not line or not line.startswith("data:"):
@@ -72,8 +87,10 @@ class VLLMHandler:
 
     # ------------------------------------------------------------------ request tracking
     def _params(self, messages, temperature, max_tokens, top_p, stop, tools,
-                tool_choice=None, extra: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                tool_choice=None, extra: Optional[Dict[str, Any]] = None,
+                penalties: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         body: Dict[str, Any] = {"model": self.model, "messages": messages, "stream": True}
+        body.update(remote_penalties(penalties))
         for k, v in (("temperature", temperature), ("max_tokens", max_tokens), ("top_p", top_p),
                      ("stop", stop), ("tools", tools)):
             if v is not None:
@@ -107,13 +124,15 @@ class VLLMHandler:
     def generate_stream(self, messages: List[Dict[str, str]], temperature: Optional[float] = None,
                         max_tokens: Optional[int] = None, top_p: Optional[float] = None,
                         stop: Optional[List[str]] = None, tools: Optional[List[Dict]] = None,
-                        request_id: Optional[str] = None) -> Generator[str, None, None]:
+                        request_id: Optional[str] = None,
+                        penalties: Optional[Dict[str, Any]] = None) -> Generator[str, None, None]:
         req_id = request_id or f"vllm-{uuid.uuid4()}"
         self._register(req_id)
         try:
             with httpx.Client(timeout=self.timeout, headers=self._headers) as c:
                 with c.stream("POST", self.base_url + "/chat/completions",
-                              json=self._params(messages, temperature, max_tokens, top_p, stop, tools)) as r:
+                              json=self._params(messages, temperature, max_tokens, top_p, stop, tools,
+                                                penalties=penalties)) as r:
                     r.raise_for_status()
                     for chunk in _sse_payloads(r.iter_lines()):
                         if self._cancelled(req_id):
@@ -134,13 +153,16 @@ class VLLMHandler:
     async def generate_stream_async(self, messages: List[Dict[str, str]], temperature: Optional[float] = None,
                                     max_tokens: Optional[int] = None, top_p: Optional[float] = None,
                                     stop: Optional[List[str]] = None, tools: Optional[List[Dict]] = None,
-                                    request_id: Optional[str] = None) -> AsyncGenerator[str, None]:
+                                    request_id: Optional[str] = None,
+                                    penalties: Optional[Dict[str, Any]] = None
+                                    ) -> AsyncGenerator[str, None]:
         req_id = request_id or f"vllm-async-{uuid.uuid4()}"
         self._register(req_id)
         try:
             async with httpx.AsyncClient(timeout=self.timeout, headers=self._headers) as c:
                 async with c.stream("POST", self.base_url + "/chat/completions",
-                                    json=self._params(messages, temperature, max_tokens, top_p, stop, tools)) as r:
+                                    json=self._params(messages, temperature, max_tokens, top_p, stop, tools,
+                                                penalties=penalties)) as r:
                     r.raise_for_status()
                     async for line in r.aiter_lines():
                         if self._cancelled(req_id):

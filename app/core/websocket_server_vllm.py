@@ -40,7 +40,22 @@ from app.utils.logger import get_logger
 logger = get_logger(__name__)
 
 GEN_KEYS = ("temperature", "max_tokens", "top_p", "top_k", "stop", "seed", "min_tokens",
-            "ignore_eos")
+            "ignore_eos", "repetition_penalty", "presence_penalty", "frequency_penalty",
+            "logit_bias")
+GEN_ALIASES = {"repeat_penalty": "repetition_penalty"}   # Ollama's name
+
+
+def gen_config(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The generation keys of a ``start_session`` / ``update_config`` config, aliases
+    resolved and the penalty fields validated (ValueError -> the ``error`` frame)."""
+    from fasttalk_llm_microservice_amd.engine.sampling_params import pick_penalties
+
+    out = {k: cfg[k] for k in GEN_KEYS if k in cfg}
+    for alias, k in GEN_ALIASES.items():
+        if alias in cfg and k not in out:
+            out[k] = cfg[alias]
+    pick_penalties(out)
+    return out
 AGENT_KEYS = ("enable_web_search", "enable_tools", "system_prompt", "vllm_model", "vllm_base_url")
 
 
@@ -362,9 +377,14 @@ class WebSocketLLMServer:
         cfg = message.get("config") or {}
         if not isinstance(cfg, dict):
             cfg = {}
+        try:   # validated first: a refused config leaves no half-made session behind
+            gen = gen_config(cfg)
+        except (ValueError, TypeError) as e:
+            await send({"type": "error", "error": {"code": "invalid_config", "message": str(e)}})
+            return
         self.conversation_manager.create_session(session_id=session_id,
                                                  system_prompt=cfg.get("system_prompt"))
-        self.connection_manager.update_config(session_id, {k: cfg[k] for k in GEN_KEYS if k in cfg})
+        self.connection_manager.update_config(session_id, gen)
         await send({"type": "session_configured", "config": cfg, "provider": self.provider})
         self.connection_manager.record_message_sent(session_id)
 
@@ -382,6 +402,12 @@ class WebSocketLLMServer:
         for k in ("stop", "seed", "min_tokens", "ignore_eos"):
             if k in sc:
                 out[k] = sc[k]
+        # penalties: what the session set, over the service defaults (DEFAULT_*_PENALTY)
+        out["penalties"] = {
+            "repetition_penalty": sc.get("repetition_penalty", c.default_repetition_penalty),
+            "presence_penalty": sc.get("presence_penalty", c.default_presence_penalty),
+            "frequency_penalty": sc.get("frequency_penalty", c.default_frequency_penalty),
+            "logit_bias": sc.get("logit_bias")}
         return out
 
     async def _handle_user_message(self, session_id: str, message: Dict[str, Any], send):
@@ -483,7 +509,7 @@ class WebSocketLLMServer:
                 messages, temperature=g["temperature"], max_tokens=g["max_tokens"], top_p=g["top_p"],
                 top_k=g["top_k"], stop=g.get("stop"), request_id=session_id, session_id=session_id,
                 seed=g.get("seed"), ignore_eos=bool(g.get("ignore_eos", False)),
-                min_tokens=int(g.get("min_tokens", 0) or 0)):
+                min_tokens=int(g.get("min_tokens", 0) or 0), penalties=g["penalties"]):
             if out.token_ids or out.text:
                 await self._emit(session_id, send, turn, out.text, len(out.token_ids), t0)
             if out.ttft_s is not None and turn.engine_ttft is None:
@@ -510,7 +536,7 @@ class WebSocketLLMServer:
                 user_message=user_text, context=ctx, temperature=g["temperature"],
                 max_tokens=g["max_tokens"], top_p=g["top_p"], top_k=g["top_k"], stop=g.get("stop"),
                 seed=g.get("seed"), ignore_eos=bool(g.get("ignore_eos", False)),
-                min_tokens=int(g.get("min_tokens", 0) or 0)):
+                min_tokens=int(g.get("min_tokens", 0) or 0), penalties=g["penalties"]):
             if ev.text or ev.num_tokens:
                 await self._emit(session_id, send, turn, ev.text, ev.num_tokens, t0)
             if ev.engine_ttft_s is not None and turn.engine_ttft is None:
@@ -527,7 +553,8 @@ class WebSocketLLMServer:
         t0 = time.time()
         async for tok in self.vllm_handler.generate_stream_async(
                 messages=messages, temperature=g["temperature"], max_tokens=g["max_tokens"],
-                top_p=g["top_p"], stop=g.get("stop"), request_id=session_id):
+                top_p=g["top_p"], stop=g.get("stop"), request_id=session_id,
+                penalties=g["penalties"]):
             await self._emit(session_id, send, turn, tok, 1, t0)
 
     async def _generate_with_ollama(self, session_id: str, send, turn: _Turn):
@@ -535,7 +562,8 @@ class WebSocketLLMServer:
         g = self._gen_settings(session_id)
         gen = self.ollama_handler.generate_stream(
             messages=messages, temperature=g["temperature"], max_tokens=g["max_tokens"],
-            top_p=g["top_p"], top_k=g["top_k"], stop=g.get("stop"), request_id=session_id)
+            top_p=g["top_p"], top_k=g["top_k"], stop=g.get("stop"), request_id=session_id,
+            penalties=g["penalties"])
         loop = asyncio.get_running_loop()
         q: "asyncio.Queue" = asyncio.Queue()
         sentinel = object()
@@ -586,7 +614,12 @@ class WebSocketLLMServer:
         cfg = message.get("config") or {}
         if not isinstance(cfg, dict):
             cfg = {}
-        self.connection_manager.update_config(session_id, {k: cfg[k] for k in GEN_KEYS if k in cfg})
+        try:
+            gen = gen_config(cfg)
+        except (ValueError, TypeError) as e:
+            await send({"type": "error", "error": {"code": "invalid_config", "message": str(e)}})
+            return
+        self.connection_manager.update_config(session_id, gen)
         agent_level = {k: v for k, v in cfg.items() if k in AGENT_KEYS}
         if self.voice_agent is not None and agent_level:
             self.voice_agent.update_config(**agent_level)

@@ -94,6 +94,13 @@ class Config:
     default_context_window: int = field(default_factory=lambda: int(_e("DEFAULT_CONTEXT_WINDOW", "8192")))
     default_top_p: float = field(default_factory=lambda: float(_e("DEFAULT_TOP_P", "0.9")))
     default_top_k: int = field(default_factory=lambda: int(_e("DEFAULT_TOP_K", "40")))
+    # sampler penalties a session does not set itself (1.0 / 0.0 / 0.0 = off)
+    default_repetition_penalty: float = field(
+        default_factory=lambda: float(_e("DEFAULT_REPETITION_PENALTY", "1.0")))
+    default_presence_penalty: float = field(
+        default_factory=lambda: float(_e("DEFAULT_PRESENCE_PENALTY", "0.0")))
+    default_frequency_penalty: float = field(
+        default_factory=lambda: float(_e("DEFAULT_FREQUENCY_PENALTY", "0.0")))
     # ---- server
     host: str = field(default_factory=lambda: _e("LLM_HOST", "0.0.0.0"))
     port: int = field(default_factory=lambda: int(_e("LLM_PORT", "8000")))
@@ -143,6 +150,12 @@ class Config:
             (0.0 <= self.default_top_p <= 1.0, f"top_p must be between 0.0 and 1.0, got {self.default_top_p}"),
             (self.default_top_k >= 1, f"top_k must be >= 1, got {self.default_top_k}"),
             (self.default_max_tokens >= 1, f"max_tokens must be >= 1, got {self.default_max_tokens}"),
+            (self.default_repetition_penalty > 0.0,
+             f"repetition_penalty must be > 0, got {self.default_repetition_penalty}"),
+            (-2.0 <= self.default_presence_penalty <= 2.0,
+             f"presence_penalty must be between -2.0 and 2.0, got {self.default_presence_penalty}"),
+            (-2.0 <= self.default_frequency_penalty <= 2.0,
+             f"frequency_penalty must be between -2.0 and 2.0, got {self.default_frequency_penalty}"),
             (1024 <= self.port <= 65535, f"Port must be between 1024 and 65535, got {self.port}"),
             (1024 <= self.monitoring_port <= 65535,
              f"Monitoring port must be between 1024 and 65535, got {self.monitoring_port}"),
@@ -193,7 +206,9 @@ class Config:
     def to_dict(self) -> Dict[str, Any]:
         keys = ["llm_provider", "compute_device", "model_name", "device", "host", "port",
                 "monitoring_port", "max_connections", "default_temperature", "default_max_tokens",
-                "default_context_window", "default_top_p", "default_top_k", "num_threads",
+                "default_context_window", "default_top_p", "default_top_k",
+                "default_repetition_penalty", "default_presence_penalty",
+                "default_frequency_penalty", "num_threads",
                 "num_workers", "log_level"]
         d: Dict[str, Any] = {k: getattr(self, k) for k in keys}
         if self.llm_provider in ("vllm", "openai"):

@@ -26,6 +26,9 @@ def main():
     ap.add_argument("--kv-blocks", type=int, default=None)
     ap.add_argument("--batch-invariant", action="store_true")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8"])
+    # sampler penalties on every row (the decode graph then runs apply -> sample -> update)
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--frequency-penalty", type=float, default=0.0)
     a = ap.parse_args()
 
     import numpy as np
@@ -44,7 +47,9 @@ def main():
     res = []
     for r in range(a.rounds):
         prompts = [rng.integers(0, 120000, a.prompt).tolist() for _ in range(a.seqs)]
-        sp = SamplingParams(temperature=a.temperature, top_p=0.9, max_tokens=a.gen, ignore_eos=True)
+        sp = SamplingParams(temperature=a.temperature, top_p=0.9, max_tokens=a.gen, ignore_eos=True,
+                            repetition_penalty=a.repetition_penalty,
+                            frequency_penalty=a.frequency_penalty)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i, p in enumerate(prompts):
@@ -61,7 +66,8 @@ def main():
         m = eng.metrics()
         res.append({"round": r, "tokens": ntok, "seconds": dt, "tok_s": ntok / dt,
                     "ttft_s": first, "decode_step_ms": m["decode_step_ms_avg"],
-                    "prefill_step_ms": m["prefill_step_ms_avg"]})
+                    "prefill_step_ms": m["prefill_step_ms_avg"],
+                    "penalty_steps": m["penalty_steps"]})
         print(json.dumps(res[-1]), flush=True)
     print(json.dumps({"final": res[-1], "runner": eng.runner.stats}), flush=True)
 

@@ -64,7 +64,7 @@ def main():
     h = r.decode_launch(seqs)
     r.decode_collect(h)
     nb = r._bucket(len(seqs))
-    g = r.graphs[nb]
+    g = r.graphs[(nb, False)]
     st = r.stg[0]
     nw = 10 * r.max_decode_batch + nb * r.max_blocks_per_seq
 

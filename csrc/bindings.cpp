@@ -41,6 +41,16 @@ int ft_sample(int* out_tokens, const void* logits, int logits_is_bf16, long logi
               const int* top_k, const long long* seeds, const int* steps,
               const uint32_t* allow_mask, int mask_words, float* ws, hipStream_t stream);
 int ft_sample_ws_floats();
+int ft_penalty_max_bias();
+int ft_penalty_apply(const void* logits, void* out, int is_bf16, long lstride, long ostride, int rows,
+                     int vocab, const int* slots, const float* rep, const float* pres,
+                     const float* freq, const void* table, long tstride, int num_slots,
+                     const int* bias_ids, const float* bias_vals, hipStream_t stream);
+int ft_penalty_update(void* table, long tstride, int num_slots, int vocab, const int* slots,
+                      const int* sampled, int rows, hipStream_t stream);
+int ft_penalty_seed(void* table, long tstride, int num_slots, int vocab, int slot, const int* ids,
+                    const int* vals, int n, int* bias_ids, float* bias_vals, const int* src_ids,
+                    const float* src_vals, hipStream_t stream);
 int ft_kv_block_copy(void* k_cache, void* v_cache, const int* src_dst, int num_pairs,
                      long block_elems, int num_blocks, hipStream_t stream);
 int ft_w4_gemm(const void* x, int x_stride, int M, const uint32_t* wq, const void* sz, int N, int K,
@@ -382,6 +392,94 @@ void sample(at::Tensor out_tokens, at::Tensor logits, at::Tensor temperature, at
                      steps.data_ptr<int>(), mp, words, one_wg ? nullptr : ws.data_ptr<float>(),
                      cur_stream()),
            "sample");
+}
+
+// penalties (csrc/kernels/penalties.hip): table int16/uint16 [S, V] (rows may be padded:
+// stride(0) >= V), bias_ids int32 [S, 300], bias_vals fp32 [S, 300]
+void check_pen_state(const at::Tensor& table, const at::Tensor& bias_ids,
+                     const at::Tensor& bias_vals) {
+  check_dev(table, "table");
+  TORCH_CHECK(table.dim() == 2 && table.stride(1) == 1 && table.element_size() == 2 &&
+                  (table.scalar_type() == at::kShort || table.scalar_type() == at::kUInt16),
+              "table must be 16-bit integers [S, V] with contiguous rows");
+  check_i32(bias_ids, "bias_ids");
+  check_dev(bias_vals, "bias_vals");
+  const int64_t nb = ft_penalty_max_bias();
+  TORCH_CHECK(bias_vals.scalar_type() == at::kFloat && bias_vals.is_contiguous(), "bias_vals fp32");
+  TORCH_CHECK(bias_ids.dim() == 2 && bias_ids.size(0) == table.size(0) && bias_ids.size(1) == nb &&
+                  bias_vals.dim() == 2 && bias_vals.size(0) == table.size(0) &&
+                  bias_vals.size(1) == nb,
+              "bias lists must be [S, ", nb, "]");
+}
+
+void penalty_apply(at::Tensor logits, at::Tensor slots, at::Tensor rep, at::Tensor pres,
+                   at::Tensor freq, at::Tensor table, at::Tensor bias_ids, at::Tensor bias_vals,
+                   at::Tensor out) {
+  check_dev(logits, "logits");
+  check_dev(out, "out");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits [B, V] with contiguous rows");
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(is_bf16 || logits.scalar_type() == at::kFloat, "logits fp32 or bf16");
+  TORCH_CHECK(out.scalar_type() == logits.scalar_type() && out.dim() == 2 && out.stride(1) == 1 &&
+                  out.size(0) == logits.size(0) && out.size(1) == logits.size(1),
+              "out must match logits");
+  // rows either coincide (in place) or do not overlap at all
+  TORCH_CHECK(out.data_ptr() != logits.data_ptr() || out.stride(0) == logits.stride(0),
+              "in-place out needs the logits' row stride");
+  check_pen_state(table, bias_ids, bias_vals);
+  const int rows = (int)logits.size(0), vocab = (int)logits.size(1);
+  TORCH_CHECK(table.size(1) == vocab, "table vocab");
+  check_i32(slots, "slots");
+  for (const at::Tensor* t : {&rep, &pres, &freq}) {
+    check_dev(*t, "rep/pres/freq");
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() >= rows,
+                "rep/pres/freq fp32 [B]");
+  }
+  TORCH_CHECK(slots.numel() >= rows, "slots length");
+  check_rc(ft_penalty_apply(logits.data_ptr(), out.data_ptr(), is_bf16 ? 1 : 0,
+                            (long)logits.stride(0), (long)out.stride(0), rows, vocab,
+                            slots.data_ptr<int>(), rep.data_ptr<float>(), pres.data_ptr<float>(),
+                            freq.data_ptr<float>(), table.data_ptr(), (long)table.stride(0),
+                            (int)table.size(0), bias_ids.data_ptr<int>(),
+                            bias_vals.data_ptr<float>(), cur_stream()),
+           "penalty_apply");
+}
+
+void penalty_update(at::Tensor table, at::Tensor slots, at::Tensor sampled) {
+  check_dev(table, "table");
+  TORCH_CHECK(table.dim() == 2 && table.stride(1) == 1 && table.element_size() == 2, "table");
+  check_i32(slots, "slots");
+  check_i32(sampled, "sampled");
+  const int rows = (int)sampled.numel();
+  TORCH_CHECK(slots.numel() >= rows, "slots length");
+  check_rc(ft_penalty_update(table.data_ptr(), (long)table.stride(0), (int)table.size(0),
+                             (int)table.size(1), slots.data_ptr<int>(), sampled.data_ptr<int>(),
+                             rows, cur_stream()),
+           "penalty_update");
+}
+
+// ids / vals: int32 [n] unique tokens and their uint16 table values; src_ids int32 [300]
+// (-1 padded) / src_vals fp32 [300]: the slot's bias list
+void penalty_seed(at::Tensor table, int64_t slot, at::Tensor ids, at::Tensor vals,
+                  at::Tensor bias_ids, at::Tensor bias_vals, at::Tensor src_ids,
+                  at::Tensor src_vals) {
+  check_pen_state(table, bias_ids, bias_vals);
+  check_i32(ids, "ids");
+  check_i32(vals, "vals");
+  check_i32(src_ids, "src_ids");
+  check_dev(src_vals, "src_vals");
+  const int64_t nb = ft_penalty_max_bias();
+  TORCH_CHECK(vals.numel() == ids.numel(), "ids / vals length");
+  TORCH_CHECK(src_ids.numel() == nb && src_vals.numel() == nb &&
+                  src_vals.scalar_type() == at::kFloat && src_vals.is_contiguous(),
+              "bias list of ", nb, " entries");
+  TORCH_CHECK(slot >= 0 && slot < table.size(0), "slot out of range");
+  check_rc(ft_penalty_seed(table.data_ptr(), (long)table.stride(0), (int)table.size(0),
+                           (int)table.size(1), (int)slot, ids.data_ptr<int>(),
+                           vals.data_ptr<int>(), (int)ids.numel(), bias_ids.data_ptr<int>(),
+                           bias_vals.data_ptr<float>(), src_ids.data_ptr<int>(),
+                           src_vals.data_ptr<float>(), cur_stream()),
+           "penalty_seed");
 }
 
 void kv_block_copy(at::Tensor k_cache, at::Tensor v_cache, at::Tensor src_dst) {
@@ -955,6 +1053,7 @@ FT_HOOK_DECL(fused_epilogue)
 FT_HOOK_DECL(norm_act)
 FT_HOOK_DECL(sampling)
 FT_HOOK_DECL(kv_copy)
+FT_HOOK_DECL(penalties)
 #undef FT_HOOK_DECL
 }
 
@@ -967,7 +1066,7 @@ void set_kernel_checks(torch::Tensor word) {
   const Hook hooks[] = {ft_check_hook_attn_decode, ft_check_hook_attn_prefill,
                         ft_check_hook_rope_kv,     ft_check_hook_fused_epilogue,
                         ft_check_hook_norm_act,    ft_check_hook_sampling,
-                        ft_check_hook_kv_copy};
+                        ft_check_hook_kv_copy,     ft_check_hook_penalties};
   for (Hook h : hooks) check_rc(h(w), "set_kernel_checks");
 }
 #endif
@@ -1007,6 +1106,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample", &sample, py::arg("out_tokens"), py::arg("logits"), py::arg("temperature"),
         py::arg("top_p"), py::arg("top_k"), py::arg("seeds"), py::arg("steps"),
         py::arg("mask") = py::none());
+  m.def("penalty_apply", &penalty_apply);
+  m.def("penalty_update", &penalty_update);
+  m.def("penalty_seed", &penalty_seed);
+  m.def("penalty_max_bias", []() { return (int64_t)ft_penalty_max_bias(); });
   m.def("kv_block_copy", &kv_block_copy);
   m.def("kv_swap", &kv_swap, py::arg("ptrs"), py::arg("ids"), py::arg("staging"),
         py::arg("block_elems"), py::arg("to_staging"), py::arg("num_blocks") = 0);

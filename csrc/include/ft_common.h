@@ -181,6 +181,8 @@ enum FtCheckCode : int {
   kCkTokenId = 4,      // embedding: input id >= vocab
   kCkSampled = 5,      // sampler: sampled id >= vocab
   kCkCopyBlock = 6,    // KV copy / swap: block id >= num_blocks
+  kCkPenSlot = 7,      // penalties: state slot >= max_num_seqs
+  kCkPenToken = 8,     // penalties: sampled / seeded / biased token id >= vocab
 };
 }  // namespace ft
 

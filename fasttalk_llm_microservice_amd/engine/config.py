@@ -84,8 +84,14 @@ class EngineConfig:
     # scratch, "int4" as below) | "image" | "scratch" | "int4": the W4 GEMM straight on
     # the int4 image (w4_packed_gemm.hip), no bf16 copy of any projection
     w4_prefill: str = "auto"
+    # sampler penalties (repetition / presence / frequency / logit_bias): a uint16 table
+    # [max_num_seqs, vocab] on the device, 66 MB at 256 x 128,256.  None: ENGINE_PENALTIES
+    # (default on).  Off: nothing is allocated and such requests are refused.
+    penalties: Optional[bool] = None
 
     def __post_init__(self):
+        if self.penalties is None:
+            self.penalties = _bool(os.environ.get("ENGINE_PENALTIES", "1") or "1")
         self.check_kv_scales()
         self.check_w4_prefill()
 

@@ -130,6 +130,17 @@ class LLMEngine:
         self.mixed_chain_guided = self.mixed_chain and \
             os.environ.get("ENGINE_MIXED_CHAIN_GUIDED", "1") != "0"
         self._last_complete = 0.0
+        # penalties (SamplingParams.has_penalties): free list of the runner's state slots,
+        # slot -> owner, and the unfinished requests that asked for penalties (the slot
+        # bookkeeping below runs only while there is one)
+        n_pen = int(getattr(runner, "pen_slots", 0) or 0)
+        self._pen_total = n_pen
+        self._pen_free: List[int] = list(range(n_pen - 1, -1, -1))
+        self._pen_owner: Dict[int, Sequence] = {}
+        self._pen_reqs: set = set()
+        # FT_PENALTY_VERIFY=1 (tests, debugging): a finishing sequence's slot is read back
+        # and compared with the host's truth (_pen_verify)
+        self.pen_verify = os.environ.get("FT_PENALTY_VERIFY", "0") == "1"
         from .debug import FaultInjector, StepProfiler
 
         self._faults = FaultInjector()
@@ -146,7 +157,11 @@ class LLMEngine:
         if len(prompt_ids) >= self.max_model_len:
             raise EngineError(f"prompt of {len(prompt_ids)} tokens exceeds max_model_len "
                               f"{self.max_model_len}")
+        if params.has_penalties:
+            self._check_penalties(params)
         seq = Sequence(request_id, prompt_ids, params, on_output, meta)
+        if params.has_penalties:
+            self._pen_reqs.add(request_id)
         seq.background = bool(background)
         if self._trace_path:
             self._trace.append(("arrive", time.perf_counter(), len(prompt_ids)))
@@ -166,6 +181,88 @@ class LLMEngine:
         self.scheduler.add(seq)
         self.stats["requests"] += 1
         return seq
+
+    # ------------------------------------------------------------------ penalties
+    # A sequence with has_penalties holds a slot of the runner's device state while it is
+    # sampled: taken (and seeded from host truth: prompt_ids -> prompt bits, output_ids ->
+    # counts) when a step first samples it and on every re-admission after a recompute or
+    # swap preemption, given back on finish, abort and preemption.  INVARIANT (runner.py,
+    # above _pen_arrays): when a step that samples a row with slot s is launched, table[s]
+    # equals the host's truth plus the tokens sampled by the sequence's still-queued steps.
+    # While its grammar is bound a sequence holds no slot (its rows carry -1): jump-forward
+    # tokens and dropped samples exist only then, so they never desynchronise a table.  A
+    # lazy grammar is undecided only for the first token: the step that samples it is a
+    # prefill, and a step queued behind it for that row has its sampler deferred
+    # (_launch_decode: defer when any row has a grammar; _speculate_mixed: its decode rows
+    # come from `running`, which the row joins in post_step), and a deferred sampler
+    # reads the slots when it is queued -- after the host decided.
+    def _check_penalties(self, params: SamplingParams):
+        if self.cfg.tp_size > 1:
+            raise EngineError("penalties are not supported with tensor parallelism yet")
+        if not self._pen_total:
+            raise EngineError("penalties are off on this engine (ENGINE_PENALTIES=0)")
+        vocab = self.model_cfg.vocab_size
+        for t in (params.logit_bias or ()):
+            if not 0 <= t < vocab:
+                raise ValueError(f"logit_bias token id {t} is outside the vocabulary [0, {vocab})")
+
+    @staticmethod
+    def _pen_wants(q: Sequence) -> bool:
+        return not (q.grammar is not None and not q.lazy) and q.params.has_penalties
+
+    def _pen_assign(self, seqs):
+        """Slots for the rows a step is about to sample."""
+        if not self._pen_reqs:
+            return
+        for q in seqs:
+            if q.pen_slot < 0 and self._pen_wants(q):
+                if not self._pen_free:
+                    raise EngineError("no free penalty slot")
+                q.pen_slot = self._pen_free.pop()
+                self._pen_owner[q.pen_slot] = q
+                self.runner.pen_active = True
+                self.runner.pen_seed(q.pen_slot, q.tokens[:q.prompt_len], q.output_ids,
+                                     q.params.logit_bias)
+
+    def _pen_release(self, q: Sequence):
+        if q.pen_slot >= 0:
+            self._pen_owner.pop(q.pen_slot, None)
+            self._pen_free.append(q.pen_slot)
+            q.pen_slot = -1
+            self.runner.pen_active = bool(self._pen_owner)
+
+    def _pen_sweep(self, batch: Optional[ScheduledBatch]):
+        """After scheduling (nothing is queued then): sequences the scheduler preempted
+        give their slots back; they are seeded afresh when they are sampled again."""
+        if not self._pen_owner:
+            return
+        keep = {id(q) for q in batch.sampled_seqs()} if batch is not None else set()
+        for q in list(self._pen_owner.values()):
+            if q.status != SeqStatus.RUNNING and id(q) not in keep:
+                self._pen_release(q)
+
+    def _pen_verify(self, q: Sequence):
+        """FT_PENALTY_VERIFY: the slot's row against the host's truth -- the prompt bits
+        are equal, no device count is below the host's, and the surplus is exactly the
+        tokens of the steps still queued for the sequence."""
+        from ..ops import PEN_COUNT_MAX, PEN_PROMPT_BIT
+
+        row = self.runner.pen_read(q.pen_slot).astype(np.int64)
+        v = row.shape[0]
+        prompt = np.zeros(v, bool)
+        prompt[q.tokens[:q.prompt_len]] = True
+        host = np.minimum(np.bincount(np.asarray(q.output_ids, np.int64), minlength=v), PEN_COUNT_MAX)
+        diff = (row & PEN_COUNT_MAX) - host
+        if not np.array_equal((row & PEN_PROMPT_BIT) != 0, prompt):
+            raise EngineError(f"penalty slot {q.pen_slot} of {q.request_id}: prompt bits differ")
+        # (a queued step whose sampler is still deferred has not counted its token yet)
+        queued = sum(1 for e in self._inflight if not getattr(e.handle, "pending", False)
+                     and any(s is q for s in e.batch.sampled_seqs()))
+        if (diff < 0).any() or int(diff.sum()) != queued:
+            raise EngineError(f"penalty slot {q.pen_slot} of {q.request_id}: device counts are "
+                              f"{int(diff.sum())} ahead of the host ({int((diff < 0).sum())} "
+                              f"behind), {queued} step(s) queued")
+        self.stats["penalty_verified"] += 1
 
     def abort(self, request_id: str) -> bool:
         seq = self.scheduler.abort(request_id)
@@ -220,6 +317,7 @@ class LLMEngine:
         of that step each sequence sat in; None = the same rows).  A guided batch
         queued ahead (``from_device``) defers its sampler until its masks are known."""
         defer = from_device and any(q.grammar is not None for q in seqs)
+        self._pen_assign(seqs)
         h = self.runner.decode_launch(seqs, ahead=int(from_device), masks=masks,
                                       rowmap=rowmap if from_device else None,
                                       **({"defer_sample": True} if defer else {}))
@@ -350,16 +448,25 @@ class LLMEngine:
         if any((id(q) not in pos and q.inflight) or (q.grammar is not None and not guided)
                or q.drop_next for q in running):
             return skip("rows")
+        # prompts a queued mixed step completes join `running` only in its post_step: they
+        # count against max_num_seqs here, or a chain of mixed steps admits more sequences
+        # than the engine (decode rows, graph buckets, penalty slots) is sized for
+        limbo = sum(1 for e in self._inflight if e.mixed
+                    for q, sm in zip(e.batch.prefill_seqs, e.batch.prefill_sample)
+                    if sm and q.status == SeqStatus.WAITING)
+        if len(running) + limbo >= sched.max_num_seqs:
+            return skip("seqs")
         if not self._grow_for_next(running):
             return skip("blocks")
         pseqs, ptok, psamp, rejected = sched._schedule_prefill(sched.max_tokens - len(running),
-                                                               len(running))
+                                                               len(running), reserved=limbo)
         for q in rejected:   # only background warm-ups are dropped while sequences run
             sched.by_id.pop(q.request_id, None)
             self._finalize(q, "abort", emit=False)
         if not pseqs:
             return skip("no_prefill")
         mb = sched.stamp(ScheduledBatch(running, pseqs, ptok, psamp))
+        self._pen_assign(mb.sampled_seqs())
         rowmap = [pos.get(id(q), -1) for q in running]
         # guided decode rows: their masks wait for the tokens of the step queued ahead,
         # so the sampler is queued once those are processed (_step_pipelined); guided
@@ -538,6 +645,15 @@ class LLMEngine:
         discard = getattr(self.runner, "discard_pending", None)
         if discard is not None:
             discard()
+        # the dropped steps may or may not have counted their tokens: every live slot is
+        # set back to the host's truth
+        for slot, q in list(self._pen_owner.items()):
+            try:
+                self.runner.pen_seed(slot, q.tokens[:q.prompt_len], q.output_ids,
+                                     q.params.logit_bias)
+            except Exception:   # (a faulted device: the caller is failing these sequences)
+                log.exception("penalty slot %d could not be re-seeded", slot)
+                self._pen_release(q)
 
     def fail_unfinished(self, error: str, reset_cache: bool = False):
         """After a failed step: every unfinished sequence ends with an error and
@@ -572,8 +688,10 @@ class LLMEngine:
         self._last_complete = 0.0
         ts = time.perf_counter()
         batch = self.scheduler.schedule()
+        self._pen_sweep(batch)
         if batch is None:
             return []
+        self._pen_assign(batch.sampled_seqs())
         t0 = time.perf_counter()
         outs: List[RequestOutput] = []
         if batch.swap_out or batch.swap_in:  # E6: host swap copies precede the forward
@@ -691,6 +809,7 @@ class LLMEngine:
             if st >= 0:
                 seq.grammar_state = st
                 self.stats["lazy_grammar_bound"] += 1
+                self._pen_release(seq)   # bound: its rows carry no slot from here on
             else:
                 seq.grammar = None
         elif seq.grammar is not None:
@@ -778,6 +897,14 @@ class LLMEngine:
         if seq.status != SeqStatus.FINISHED or seq.block_ids:
             self.scheduler.finish(seq, reason)
         seq.finish_reason = reason
+        if seq.pen_slot >= 0:
+            try:
+                if self.pen_verify and reason != "error":
+                    self._pen_verify(seq)
+            finally:
+                self._pen_release(seq)
+        if self._pen_reqs:
+            self._pen_reqs.discard(seq.request_id)
         if seq.grammar is not None:   # output lengths of guided sequences (tool calls, JSON)
             self._guided_lens.append(seq.num_output)
         tail = ""
@@ -878,6 +1005,8 @@ class LLMEngine:
             "prefix_cache_hit_rate": (self.bm.hits / self.bm.queries) if self.bm.queries else 0.0,
             "preemptions": self.scheduler.num_preemptions,
             "guided_capped_steps": self.scheduler.guided_capped,
+            "penalty_slots_in_use": len(self._pen_owner),
+            "penalty_steps": int(getattr(self.runner, "stats", {}).get("penalty_steps", 0)),
             "swapped": len(self.scheduler.swapped),
             "swap_outs": self.scheduler.num_swap_out,
             "swap_ins": self.scheduler.num_swap_in,

@@ -40,7 +40,8 @@ class KernelCheckError(RuntimeError):
 
     CODES = {1: "block-table entry >= num_blocks", 2: "KV slot >= pool capacity",
              3: "position >= rotary table rows", 4: "input token id >= vocab",
-             5: "sampled token id >= vocab", 6: "KV copy/swap block id >= num_blocks"}
+             5: "sampled token id >= vocab", 6: "KV copy/swap block id >= num_blocks",
+             7: "penalty slot >= max_num_seqs", 8: "penalty token id >= vocab"}
 
     def __init__(self, word):
         count, code, ctx, value = (int(x) for x in word[:4])
@@ -60,6 +61,20 @@ def _pow2_ceil(x: int) -> int:
 
 def input_words(mb: int, max_blocks: int) -> int:
     return 10 * mb + mb * max_blocks
+
+
+def pen_words(mb: int) -> int:
+    """int32 words of a step's per-row penalty arrays: slot | rep | pres | freq.  They sit
+    IN FRONT of the decode inputs in the staging image and the device buffer, so a step
+    with a penalised row uploads them in the same copy (it starts 4 * mb words earlier)
+    and a step without one uploads exactly what it always did."""
+    return 4 * mb
+
+
+def _pen_views(buf: torch.Tensor, mb: int):
+    """(slots int32 [mb], rep, pres, freq f32 [mb]) views of the penalty prefix."""
+    f = buf[mb:4 * mb].view(torch.float32)
+    return buf[0:mb], f[0:mb], f[mb:2 * mb], f[2 * mb:3 * mb]
 
 
 def _input_views(buf: torch.Tensor, mb: int, max_blocks: int):
@@ -135,7 +150,12 @@ class _Staging:
         i32 = torch.int32
         # one pinned int32 image, laid out like the device inputs (_input_views), so a
         # step's inputs go up in ONE copy: small | f32 | seeds (int64) | block tables
-        self.h_in = torch.zeros(input_words(mb, max_blocks), dtype=i32, pin_memory=pin)
+        pw = pen_words(mb)
+        self.h_all = torch.zeros(pw + input_words(mb, max_blocks), dtype=i32, pin_memory=pin)
+        self.h_in = self.h_all[pw:]
+        self.h_pen = tuple(v.numpy() for v in _pen_views(self.h_all, mb))
+        self.h_pen[0][:] = -1
+        self.pen = False   # the staged step has a penalised row
         self.h_small, self.h_f32, self.h_seeds, self.h_bt = _input_views(self.h_in, mb, max_blocks)
         self.h_out = torch.zeros(mb, dtype=i32, pin_memory=pin)
         self.h_err = torch.zeros(1, dtype=i32, pin_memory=pin)  # TP collective error flag
@@ -155,7 +175,7 @@ class MixedHandle:
     builds the step queued behind it once the GPU passes it).  They rotate; a
     handle is reused only after MIXED_HANDLES - 1 later mixed launches, more than
     the steps the engine keeps queued (ENGINE_PIPELINE_DEPTH + 1)."""
-    __slots__ = ("host", "event", "mark", "n", "pending", "logits", "samp")
+    __slots__ = ("host", "event", "mark", "n", "pending", "logits", "samp", "seqs")
 
     def __init__(self, rows: int, pin: bool, gpu: bool):
         self.host = torch.zeros(rows, dtype=torch.int32, pin_memory=pin)
@@ -167,6 +187,7 @@ class MixedHandle:
         self.pending = False
         self.logits = None
         self.samp = None
+        self.seqs = None   # deferred sampler: its rows (their penalty slots are read then)
 
 
 MIXED_HANDLES = 4
@@ -175,13 +196,14 @@ MIXED_HANDLES = 4
 class DecodeHandle:
     """A queued graph-replayed decode step.  ``pending``: only its forward pass is
     queued; its sampler waits for the allow-masks (``ModelRunner.sample_launch``)."""
-    __slots__ = ("stage", "n", "nb", "pending")
+    __slots__ = ("stage", "n", "nb", "pending", "seqs")
 
-    def __init__(self, stage: "_Staging", n: int, nb: int, pending: bool = False):
+    def __init__(self, stage: "_Staging", n: int, nb: int, pending: bool = False, seqs=None):
         self.stage = stage
         self.n = n
         self.nb = nb
         self.pending = pending
+        self.seqs = seqs   # deferred sampler: its rows (their penalty slots are read then)
 
 
 class ModelRunner:
@@ -258,6 +280,17 @@ class ModelRunner:
             log.warning("FT_KERNEL_CHECKS: bounds-checked kernels (KV pool %d blocks x %d, "
                         "rotary rows %d, vocab %d)", self.num_blocks, self.bs,
                         self.model.cos_sin.shape[0], self.mcfg.vocab_size)
+        # penalties: per-slot device state (ops.penalty_state), allocated after the KV pool
+        # was sized, out of the reserve _decide_num_blocks keeps back -- the pool is the
+        # size it was without them.  Single process only (the engine refuses penalties
+        # under tensor parallelism), and nothing at all with cfg.penalties off.
+        self.pen_slots = 0
+        self.pen_active = False   # the engine has handed out a slot (else steps skip the row scan)
+        self.pen_table = self.pen_bias_ids = self.pen_bias_vals = None
+        if getattr(cfg, "penalties", True) and comm.world_size == 1:
+            self.pen_slots = cfg.max_num_seqs
+            self.pen_table, self.pen_bias_ids, self.pen_bias_vals = ops.penalty_state(
+                self.pen_slots, model_cfg.vocab_size, self.device)
         # E6 host swap pool (--swap-space): capped at 2x the device pool, allocated
         # (pinned) on the first swap-out so an idle server does not pin host memory
         k0 = self.kv[0][0]
@@ -285,7 +318,12 @@ class ModelRunner:
         # each of the four it used to take: profiles/prof_driver_config_r02b.txt).
         # int32 fields: ids | pos | slots | seq_lens | top_k | steps, then temperature |
         # top_p (f32), seeds (int64), block tables
-        self.d_in = torch.zeros(input_words(mb, self.max_blocks_per_seq), dtype=i32, device=dv)
+        # (the penalty prefix in front of them is uploaded only by steps that use it)
+        pw = pen_words(mb)
+        self.d_all = torch.zeros(pw + input_words(mb, self.max_blocks_per_seq), dtype=i32, device=dv)
+        self.d_in = self.d_all[pw:]
+        self.d_pen = _pen_views(self.d_all, mb)
+        self.d_pen[0].fill_(-1)
         self.d_small, self.d_f32, self.d_seeds, self.d_bt = _input_views(self.d_in, mb, self.max_blocks_per_seq)
         self.d_input_ids = self.d_small[0:mb]
         self.d_positions = self.d_small[mb:2 * mb]
@@ -363,11 +401,12 @@ class ModelRunner:
         self._blk_event = torch.cuda.Event() if self._blk_host is not None else None
         self._blk_armed = False
         self._blk_waits = 0
-        self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        # keyed (batch bucket, pen): pen = the sampler is wrapped in the penalty kernels
+        self.graphs: Dict[Tuple[int, bool], torch.cuda.CUDAGraph] = {}
         # guided decoding, pipelined: per bucket a forward graph (-> logits) and a
         # sampler graph, so the next step's forward is queued before this step's
         # tokens are known and only its sampler waits for the grammar masks
-        self.graphs_split: Dict[int, tuple] = {}
+        self.graphs_split: Dict[Tuple[int, bool], tuple] = {}
         self._fwd_logits: Dict[int, torch.Tensor] = {}
         self._pending_split: Optional["DecodeHandle"] = None   # forward queued, sampler not yet
         # ENGINE_GUIDED_PIPELINE=0: guided batches run one synchronous step at a time
@@ -391,7 +430,8 @@ class ModelRunner:
         self._warm_left = int(os.environ.get("ENGINE_TP_WARM_STEPS", "4")) \
             if comm.world_size > 1 else 0
         self._trace_tp = os.environ.get("FT_TP_TRACE", "0") == "1" and comm.world_size > 1
-        self.stats = {"graph_replays": 0, "eager_decode": 0, "prefill_steps": 0, "captures": 0}
+        self.stats = {"graph_replays": 0, "eager_decode": 0, "prefill_steps": 0, "captures": 0,
+                      "penalty_steps": 0}
         # tests: a list here collects every step's logits (fp32; eager steps on the host,
         # graph-replayed and mixed-ahead steps as stream-ordered device copies) -- TP-vs-TP=1
         # numerics are compared on logits, not on greedy tokens of random weights.  With
@@ -399,7 +439,7 @@ class ModelRunner:
         self.logits_tap: Optional[list] = None
         self.logits_tap_ids: Optional[list] = None
         self._tap_rows: Optional[list] = None
-        self._graph_logits: Dict[int, torch.Tensor] = {}   # logits tensor of each graph
+        self._graph_logits: Dict[Tuple[int, bool], torch.Tensor] = {}   # raw logits of each graph
         # FT_GPU_GAPS=1: timing events around every graph-replayed decode step, so
         # gap_summary() can report how long the GPU sat idle BETWEEN consecutive
         # decode steps (the host enqueued the next one late), without a profiler
@@ -515,6 +555,91 @@ class ModelRunner:
             steps[i] = s.num_output + s.inflight + 131 * s.preemptions
         return temp, topp, topk, seeds, steps
 
+    # ------------------------------------------------------------------ penalties
+    # INVARIANT: when a step that samples row r with slot s is launched, table[s] equals
+    # the host's truth for that sequence (prompt tokens -> bit 15, output_ids -> counts)
+    # plus the tokens sampled by its still-queued steps.  It holds because the slot is
+    # seeded from host truth when the engine hands it out (pen_seed, stream-ordered
+    # before the step), and every sampling step that carries the slot also runs
+    # penalty_update on its sampled ids, in stream order, before the next step's
+    # penalty_apply.  A row whose grammar is bound carries slot -1: nothing is applied
+    # and nothing is counted (jump-forward tokens and dropped samples exist only then).
+    def _pen_arrays(self, seqs):
+        """(slot, rep, pres, freq) of a step's sampled rows, or None when no row holds
+        a slot (the step then launches none of the penalty kernels)."""
+        if self.pen_table is None or not self.pen_active:
+            return None
+        slot = None
+        for i, s in enumerate(seqs):
+            k = getattr(s, "pen_slot", -1)
+            if k < 0 or (s.grammar is not None and not s.lazy):
+                continue
+            if slot is None:
+                n = len(seqs)
+                slot = np.full(n, -1, np.int32)
+                rp = np.ones(n, np.float32)
+                pr = np.zeros(n, np.float32)
+                fr = np.zeros(n, np.float32)
+            p = s.params
+            slot[i] = k
+            rp[i] = p.repetition_penalty
+            pr[i] = p.presence_penalty
+            fr[i] = p.frequency_penalty
+        if slot is None:
+            return None
+        return slot, rp, pr, fr
+
+    @torch.inference_mode()   # like every launch path: the uploader's buffers are made there
+    def pen_seed(self, slot: int, prompt_ids, output_ids, bias: Optional[dict]):
+        """Sets slot ``slot`` to a sequence's host truth: prompt tokens get bit 15, output
+        tokens their (saturating) counts, ``bias`` (token id -> value) becomes the slot's
+        bias list.  Queued in stream order: steps launched afterwards see it."""
+        if self.pen_table is None:
+            raise RuntimeError("penalties are off (EngineConfig.penalties)")
+        vals: Dict[int, int] = {}
+        for t in np.unique(np.asarray(prompt_ids, dtype=np.int64)).tolist():
+            vals[t] = ops.PEN_PROMPT_BIT
+        if len(output_ids):
+            toks, cnt = np.unique(np.asarray(output_ids, dtype=np.int64), return_counts=True)
+            for t, c in zip(toks.tolist(), cnt.tolist()):
+                vals[t] = vals.get(t, 0) | min(int(c), ops.PEN_COUNT_MAX)
+        n = len(vals)
+        nb = ops.PEN_MAX_BIAS
+        img = np.zeros(2 * n + 2 * nb, np.int32)
+        img[:n] = list(vals.keys())
+        img[n:2 * n] = list(vals.values())
+        img[2 * n:2 * n + nb] = -1
+        bv = img[2 * n + nb:].view(np.float32)
+        for i, (t, b) in enumerate((bias or {}).items()):
+            img[2 * n + i] = t
+            bv[i] = b
+        # pinned, asynchronous (the uploader's images): admissions do not stall the host
+        # thread that keeps the decode pipeline fed
+        d = self._upload([img])[0] if self.is_gpu else torch.from_numpy(img)
+        ops.penalty_seed(self.pen_table, slot, d[:n], d[n:2 * n], self.pen_bias_ids,
+                         self.pen_bias_vals, d[2 * n:2 * n + nb],
+                         d[2 * n + nb:].view(torch.float32))
+
+    def pen_read(self, slot: int) -> np.ndarray:
+        """The table row of ``slot`` as uint16 (synchronises: tests / FT_PENALTY_VERIFY)."""
+        if self.is_gpu:
+            torch.cuda.synchronize(self.device)
+        return self.pen_table[slot].cpu().numpy().view(np.uint16)
+
+    def _pen_sample(self, logits, samp, dmask, pen, out=None):
+        """The sampler over ``logits`` (raw: they are left untouched), wrapped in the
+        penalty kernels when ``pen`` (device slot, rep, pres, freq) is given."""
+        temp, topp, topk, seeds, steps = samp
+        if pen is None:
+            return ops.sample(logits, temp, topp, topk, seeds, steps, out=out, mask=dmask)
+        self.stats["penalty_steps"] += 1
+        slot, rp, pr, fr = pen
+        pl = ops.penalty_apply(logits, slot, rp, pr, fr, self.pen_table, self.pen_bias_ids,
+                               self.pen_bias_vals, out=torch.empty_like(logits))
+        out = ops.sample(pl, temp, topp, topk, seeds, steps, out=out, mask=dmask)
+        ops.penalty_update(self.pen_table, slot, out[:logits.shape[0]])
+        return out
+
     def _mixed(self, batch: ScheduledBatch, masks) -> List[int]:
         host = self._mixed_host(batch)
         if self.bcast is not None:
@@ -584,6 +709,7 @@ class ModelRunner:
                     num_partials=sum(c[3] for c in combine))
         sseqs = dseqs + [s for s, sm in zip(pseqs, psamp) if sm]
         host["sampling"] = self._sampling_arrays(sseqs)
+        host["pen"] = self._pen_arrays(sseqs)
         if self.logits_tap_ids is not None:
             self._tap_rows = [s.request_id for s in sseqs]
         return host
@@ -615,10 +741,13 @@ class ModelRunner:
             names += ["d_bt", "d_sl"]
         arrays = [host[k] for k in names]
         has_logits = len(host["lrows"]) > 0
+        pen = host.get("pen") if has_logits else None
         if has_logits:
             arrays += list(host["sampling"])
             if masks is not None:
                 arrays.append(masks)
+            if pen is not None:   # same upload as the other sampling arrays
+                arrays += list(pen)
         if self.is_gpu:
             dev = self._upload(arrays)
         else:
@@ -653,7 +782,9 @@ class ModelRunner:
         k = len(names)
         samp = dev[k:k + 5]
         dmask = dev[k + 5] if masks is not None else None
-        return self._sample(h, host["sampling"], masks, dev_sampling=samp, dev_mask=dmask)
+        dpen = dev[-4:] if pen is not None else None
+        return self._sample(h, host["sampling"], masks, dev_sampling=samp, dev_mask=dmask,
+                            dev_pen=dpen)
 
     def _wait(self, ev=None):
         """Block until the GPU work queued so far (or up to ``ev``) is done WITHOUT
@@ -712,7 +843,7 @@ class ModelRunner:
         if self.d_check is not None:
             self.d_check.zero_()
 
-    def _sample(self, h, sampling, masks, dev_sampling=None, dev_mask=None) -> List[int]:
+    def _sample(self, h, sampling, masks, dev_sampling=None, dev_mask=None, dev_pen=None) -> List[int]:
         logits = self.model.compute_logits(h)
         if self.logits_tap is not None:
             self._tap(logits.float().cpu())
@@ -724,8 +855,7 @@ class ModelRunner:
                 dev = [torch.from_numpy(np.ascontiguousarray(a)) for a in arrays]
             dev_sampling = dev[:5]
             dev_mask = dev[5] if masks is not None else None
-        temp, topp, topk, seeds, steps = dev_sampling
-        out = ops.sample(logits, temp, topp, topk, seeds, steps, mask=dev_mask)
+        out = self._pen_sample(logits, dev_sampling, dev_mask, dev_pen)
         if not self.is_gpu:
             return out.tolist()
         n = out.shape[0]
@@ -818,6 +948,12 @@ class ModelRunner:
         st = self.stg[self._stg_next]
         self._stg_next = (self._stg_next + 1) % len(self.stg)
         maxblk = self._decode_fill(seqs, nb, st)
+        # penalty arrays: into the staging prefix now, or (a deferred sampler) when the
+        # sampler is queued -- whether a lazy grammar bound is known only then
+        pa = None if defer_sample else self._pen_arrays(seqs)
+        st.pen = pa is not None
+        if pa is not None:
+            self._pen_stage(st, pa, n, nb)
         gather = None
         if ahead and rowmap is not None:
             gather = np.zeros(nb, dtype=np.int64)   # padding rows read row 0 (ignored)
@@ -826,7 +962,7 @@ class ModelRunner:
         if defer_sample:
             assert self.can_defer_sample()
             self._decode_enqueue(st, nb, n, from_device=bool(ahead), gather=gather, fwd_only=True)
-            h = DecodeHandle(st, n, nb, pending=True)
+            h = DecodeHandle(st, n, nb, pending=True, seqs=list(seqs))
             self._pending_split = h
             return h
         if self.bcast is not None:
@@ -835,12 +971,13 @@ class ModelRunner:
                                        "seeds": st.hseed.copy(), "from_device": bool(ahead),
                                        "rowmap": gather}, masks))
         self._set_masks(masks, n)
-        self._decode_enqueue(st, nb, n, from_device=bool(ahead), gather=gather)
-        if self.logits_tap is not None and nb in self._graph_logits:
+        pen = st.pen
+        self._decode_enqueue(st, nb, n, from_device=bool(ahead), gather=gather, pen=pen)
+        if self.logits_tap is not None and (nb, pen) in self._graph_logits:
             # copied in stream order: the next queued replay overwrites the graph's logits
             if self.logits_tap_ids is not None:
                 self._tap_rows = [s.request_id for s in seqs]
-            self._tap(self._graph_logits[nb][:n].float().clone())
+            self._tap(self._graph_logits[(nb, pen)][:n].float().clone())
         return DecodeHandle(st, n, nb)
 
     @torch.inference_mode()
@@ -852,16 +989,30 @@ class ModelRunner:
         (``mixed_launch(..., defer_sample=True)``) eager sampler reads its held logits."""
         if isinstance(h, MixedHandle):
             assert h.pending
-            dmask = None
-            if masks is not None:
-                dmask = self._upload([masks])[0] if self.is_gpu else torch.from_numpy(masks)
-            self._mixed_sample(h, h.logits, h.samp, dmask)
+            pen = self._pen_arrays(h.seqs) if h.seqs is not None else None
+            arrays = ([masks] if masks is not None else []) + list(pen or ())
+            dev = []
+            if arrays:
+                dev = self._upload(arrays) if self.is_gpu else \
+                    [torch.from_numpy(np.ascontiguousarray(a)) for a in arrays]
+            dmask = dev[0] if masks is not None else None
+            self._mixed_sample(h, h.logits, h.samp, dmask, dev[-4:] if pen is not None else None)
             return
         assert h.pending and self._pending_split is h
         self._set_masks(masks, h.n)
-        self.graphs_split[h.nb][1].replay()
-        self._pending_split = None
         st = h.stage
+        # the rows' penalty slots as they stand now (a lazy grammar that bound meanwhile
+        # has given its slot back): staged and uploaded with this sampler, not the forward
+        pen = self._pen_arrays(h.seqs) if h.seqs is not None else None
+        if pen is not None:
+            self._pen_stage(st, pen, h.n, h.nb)
+            pw = pen_words(self.max_decode_batch)
+            self.d_all[:pw].copy_(st.h_all[:pw], non_blocking=True)
+            self.stats["penalty_steps"] += 1
+        key = (h.nb, pen is not None)
+        pair = self.graphs_split.get(key) or self._capture_split(h.nb, pen is not None)
+        pair[1].replay()
+        self._pending_split = None
         st.h_out[:h.n].copy_(self.d_out[:h.n], non_blocking=True)
         st.err_armed = False
         st.event.record()
@@ -948,6 +1099,11 @@ class ModelRunner:
         arrays.append(dst if partial and len(dst) else np.zeros(1, np.int64))
         if masks is not None and not defer_sample:
             arrays.append(masks)
+        # a deferred sampler reads its rows' penalty slots when it is queued (sample_launch):
+        # whether a lazy grammar bound is known only then
+        pen = None if defer_sample else host["pen"]
+        if pen is not None:
+            arrays += list(pen)
         if self.is_gpu:
             dev = self._upload(arrays)
         else:
@@ -996,10 +1152,11 @@ class ModelRunner:
             # the sampling arrays are views into the shared upload buffer, which the
             # masks' upload (sample_launch) overwrites first: keep copies
             mh.pending, mh.logits, mh.samp = True, logits, [t.clone() for t in samp]
+            mh.seqs = batch.sampled_seqs()
             self.stats["deferred_mixed"] = self.stats.get("deferred_mixed", 0) + 1
         else:
             dmask = dev[len(names) + 7] if masks is not None else None
-            self._mixed_sample(mh, logits, samp, dmask)
+            self._mixed_sample(mh, logits, samp, dmask, dev[-4:] if pen is not None else None)
         if self._gaps is not None:
             self._gap_mark(False)
         tp4 = time.perf_counter()
@@ -1012,18 +1169,24 @@ class ModelRunner:
         ml["n"] += 1
         return mh
 
-    def _mixed_sample(self, mh: "MixedHandle", logits, samp, dmask):
-        temp, topp, topk, seeds, steps = samp
-        ops.sample(logits, temp, topp, topk, seeds, steps, out=self.d_out[:mh.n], mask=dmask)
+    def _mixed_sample(self, mh: "MixedHandle", logits, samp, dmask, pen=None):
+        self._pen_sample(logits, samp, dmask, pen, out=self.d_out[:mh.n])
         mh.host[:mh.n].copy_(self.d_out[:mh.n], non_blocking=self.is_gpu)
         if mh.event is not None:
             mh.event.record()
-        mh.pending, mh.logits, mh.samp = False, None, None
+        mh.pending, mh.logits, mh.samp, mh.seqs = False, None, None, None
 
     def mixed_collect(self, h: "MixedHandle") -> List[int]:
         if h.event is not None:
             self._wait(h.event)
         return h.host[:h.n].tolist()
+
+    def _pen_stage(self, st: "_Staging", pen, n: int, nb: int):
+        """Writes a step's penalty arrays into the prefix of a pinned staging set
+        (padding rows: no slot)."""
+        hslot, hrep, hpres, hfreq = st.h_pen
+        hslot[:n], hrep[:n], hpres[:n], hfreq[:n] = pen
+        hslot[n:nb] = -1
 
     def _decode_fill(self, seqs, nb: int, st: "_Staging") -> int:
         """Writes a decode step's inputs into a pinned staging set."""
@@ -1110,11 +1273,17 @@ class ModelRunner:
         return out
 
     def _decode_enqueue(self, st: "_Staging", nb: int, n: int, from_device: bool = False,
-                        gather: Optional[np.ndarray] = None, fwd_only: bool = False):
+                        gather: Optional[np.ndarray] = None, fwd_only: bool = False,
+                        pen: bool = False):
         nw = 10 * self.max_decode_batch + nb * self.max_blocks_per_seq
         if self._gaps is not None:   # g: a split step, closed by its sampler (sample_launch)
             self._gap_mark(True, "g" if fwd_only else "d")
-        self.d_in[:nw].copy_(st.h_in[:nw], non_blocking=True)
+        if pen:   # the same copy, started at the penalty prefix
+            pw = pen_words(self.max_decode_batch)
+            self.d_all[:pw + nw].copy_(st.h_all[:pw + nw], non_blocking=True)
+            self.stats["penalty_steps"] += 1
+        else:
+            self.d_in[:nw].copy_(st.h_in[:nw], non_blocking=True)
         if from_device:  # the previous step's sampled ids feed this step
             if gather is None:
                 self.d_input_ids[:nb].copy_(self.d_out[:nb])
@@ -1133,16 +1302,16 @@ class ModelRunner:
                     self.d_input_ids.index_copy_(0, self.d_map[k:2 * k],
                                                  self.d_out.index_select(0, self.d_map[:k]))
         if fwd_only:
-            pair = self.graphs_split.get(nb)
+            pair = self.graphs_split.get((nb, False)) or self.graphs_split.get((nb, True))
             if pair is None:
-                pair = self._capture_split(nb)
+                pair = self._capture_split(nb, False)
             pair[0].replay()
             self.stats["graph_replays"] += 1
             self.stats["deferred_samples"] = self.stats.get("deferred_samples", 0) + 1
             return
-        g = self.graphs.get(nb)
+        g = self.graphs.get((nb, pen))
         if g is None:
-            g = self._capture(nb)
+            g = self._capture(nb, pen)
         g.replay()
         self.stats["graph_replays"] += 1
         st.h_out[:n].copy_(self.d_out[:n], non_blocking=True)
@@ -1206,39 +1375,55 @@ class ModelRunner:
                         dec_block_tables=self.d_bt[:nb], dec_seq_lens=self.d_seq_lens[:nb],
                         tmp_out=self.tmp_out, tmp_ml=self.tmp_ml, dec_counters=self.dec_counters)
 
-    def _graph_body(self, nb: int, keep: bool = False):
+    def _graph_sample(self, logits, nb: int, pen: bool):
+        """The sampler of a decode graph: with ``pen`` it is apply -> sample -> update,
+        the penalties applied out of place so the graph's logits stay raw (logit taps)."""
+        mask = self.d_mask[:nb] if self.d_mask is not None else None
+        if pen:
+            slot, rp, pr, fr = (t[:nb] for t in self.d_pen)
+            logits = ops.penalty_apply(logits, slot, rp, pr, fr, self.pen_table, self.pen_bias_ids,
+                                       self.pen_bias_vals, out=torch.empty_like(logits))
+        ops.sample(logits, self.d_temp[:nb], self.d_top_p[:nb], self.d_top_k[:nb],
+                   self.d_seeds[:nb], self.d_steps[:nb], out=self.d_out[:nb], mask=mask)
+        if pen:
+            ops.penalty_update(self.pen_table, slot, self.d_out[:nb])
+
+    def _graph_body(self, nb: int, keep: bool = False, pen: bool = False):
         meta = self._decode_meta(nb)
         h = self.model.forward(self.d_input_ids[:nb], meta, self.kv)
         logits = self.model.compute_logits(h)
         if keep:   # graph-pool memory: holds each replay's logits until the next one
-            self._graph_logits[nb] = logits
-        ops.sample(logits, self.d_temp[:nb], self.d_top_p[:nb], self.d_top_k[:nb],
-                   self.d_seeds[:nb], self.d_steps[:nb], out=self.d_out[:nb],
-                   mask=self.d_mask[:nb] if self.d_mask is not None else None)
+            self._graph_logits[(nb, pen)] = logits
+        self._graph_sample(logits, nb, pen)
         if self.checks_comm:
             self.comm.export_error()
 
     @torch.inference_mode()
-    def _capture_split(self, nb: int):
+    def _capture_split(self, nb: int, pen: bool = False):
         """The forward graph (-> logits, held in ``_fwd_logits``) and the sampler graph
         of bucket ``nb`` for pipelined guided decoding, captured like ``_capture``.
+        The two ``pen`` variants share the forward graph; only the sampler is captured
+        again (with the penalty kernels around it).
         Nothing replays between a step's two halves (its sampler is queued before
         the next forward), so the pool may share their temporaries with every other
         graph; the logits stay allocated."""
-        self._assert_no_pending_split("split-graph capture")
         t0 = time.time()
+        other = self.graphs_split.get((nb, not pen))
+        if other is not None:
+            # (a forward may be pending here: only the sampler runs, on its own logits)
+            return self._capture_split_sampler(nb, pen, other[0], t0)
+        self._assert_no_pending_split("split-graph capture")
         saved = (self.d_slots[:nb].clone(), self.d_seq_lens[:nb].clone())
         self.d_slots[:nb].fill_(-1)
         self.d_seq_lens[:nb].fill_(0)
+        psaved = self._pen_capture_begin(nb, pen)
 
         def fwd():
             h = self.model.forward(self.d_input_ids[:nb], self._decode_meta(nb), self.kv)
             return self.model.compute_logits(h)
 
         def samp(lg):
-            ops.sample(lg, self.d_temp[:nb], self.d_top_p[:nb], self.d_top_k[:nb],
-                       self.d_seeds[:nb], self.d_steps[:nb], out=self.d_out[:nb],
-                       mask=self.d_mask[:nb])
+            self._graph_sample(lg, nb, pen)
 
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
@@ -1256,13 +1441,44 @@ class ModelRunner:
             samp(lg)
         self.d_slots[:nb].copy_(saved[0])
         self.d_seq_lens[:nb].copy_(saved[1])
-        self.graphs_split[nb] = (gf, gs)
+        self._pen_capture_end(nb, psaved)
+        self.graphs_split[(nb, pen)] = (gf, gs)
         self.stats["captures"] += 1
-        log.info("captured split decode graphs batch=%d in %.2fs", nb, time.time() - t0)
+        log.info("captured split decode graphs batch=%d pen=%d in %.2fs", nb, pen, time.time() - t0)
         return gf, gs
 
+    def _capture_split_sampler(self, nb: int, pen: bool, gf, t0: float):
+        lg = self._fwd_logits[nb]
+        psaved = self._pen_capture_begin(nb, pen)
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            self._graph_sample(lg, nb, pen)  # warm-up (allocator)
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        gs = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gs, pool=self.graph_pool):
+            self._graph_sample(lg, nb, pen)
+        self._pen_capture_end(nb, psaved)
+        self.graphs_split[(nb, pen)] = (gf, gs)
+        self.stats["captures"] += 1
+        log.info("captured split sampler graph batch=%d pen=%d in %.2fs", nb, pen, time.time() - t0)
+        return gf, gs
+
+    def _pen_capture_begin(self, nb: int, pen: bool):
+        """Warm-up and capture runs of a penalty graph must not touch any slot's state:
+        every row's slot is -1 while they run (restored by _pen_capture_end)."""
+        if not pen:
+            return None
+        saved = self.d_pen[0][:nb].clone()
+        self.d_pen[0][:nb].fill_(-1)
+        return saved
+
+    def _pen_capture_end(self, nb: int, saved):
+        if saved is not None:
+            self.d_pen[0][:nb].copy_(saved)
+
     @torch.inference_mode()
-    def _capture(self, nb: int):
+    def _capture(self, nb: int, pen: bool = False):
         """Captures the decode graph of batch bucket ``nb``.  Always under
         inference mode, whichever path triggers it (pipelined launches run outside
         ``execute``): the CUDA generator's graph-safe RNG state is created by the
@@ -1273,21 +1489,23 @@ class ModelRunner:
         saved = (self.d_slots[:nb].clone(), self.d_seq_lens[:nb].clone())
         self.d_slots[:nb].fill_(-1)
         self.d_seq_lens[:nb].fill_(0)
+        psaved = self._pen_capture_begin(nb, pen)
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s), self._long_waits():
-            self._graph_body(nb)  # warm-up (allocator, lazy init)
+            self._graph_body(nb, pen=pen)  # warm-up (allocator, lazy init)
         torch.cuda.current_stream(self.device).wait_stream(s)
         if self.graph_pool is None:
             self.graph_pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self.graph_pool):
-            self._graph_body(nb, keep=True)
+            self._graph_body(nb, keep=True, pen=pen)
         self.d_slots[:nb].copy_(saved[0])
         self.d_seq_lens[:nb].copy_(saved[1])
-        self.graphs[nb] = g
+        self._pen_capture_end(nb, psaved)
+        self.graphs[(nb, pen)] = g
         self.stats["captures"] += 1
-        log.info("captured decode graph batch=%d in %.2fs", nb, time.time() - t0)
+        log.info("captured decode graph batch=%d pen=%d in %.2fs", nb, pen, time.time() - t0)
         return g
 
     def _decode_eager(self, seqs, masks) -> List[int]:
@@ -1317,11 +1535,16 @@ class ModelRunner:
             self.bcast.send(("warmup", list(batch_sizes or self.graph_sizes), None))
         t0 = time.time()
         split = self.can_defer_sample() and self._warm_split_graphs()
+        # ENGINE_PENALTIES_WARM=1: the penalty variants too (otherwise captured by the
+        # first step of a bucket that carries a penalised row)
+        pens = (False, True) if self.pen_table is not None and \
+            os.environ.get("ENGINE_PENALTIES_WARM", "0") == "1" else (False,)
         for b in batch_sizes or self.graph_sizes:
             b = self._bucket(b)
-            if b is not None and b not in self.graphs:
-                self._capture(b)
-            if b is not None and split and b not in self.graphs_split:
-                self._capture_split(b)
+            for pen in pens:
+                if b is not None and (b, pen) not in self.graphs:
+                    self._capture(b, pen)
+                if b is not None and split and (b, pen) not in self.graphs_split:
+                    self._capture_split(b, pen)
         log.info("decode graphs ready (%d + %d split) in %.1fs", len(self.graphs),
                  len(self.graphs_split), time.time() - t0)

@@ -9,6 +9,21 @@ import random
 from typing import Any, List, Optional
 
 
+PENALTY_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias")
+
+
+def pick_penalties(src) -> dict:
+    """The penalty fields a request dict (an OpenAI body, a WebSocket session config)
+    sets, under SamplingParams' names; Ollama's ``repeat_penalty`` is accepted for
+    ``repetition_penalty``.  Validated: raises ValueError like SamplingParams does."""
+    out = {k: src[k] for k in PENALTY_KEYS if src.get(k) is not None}
+    if "repetition_penalty" not in out and src.get("repeat_penalty") is not None:
+        out["repetition_penalty"] = src["repeat_penalty"]
+    if out:
+        SamplingParams(**out)
+    return out
+
+
 @dataclasses.dataclass
 class SamplingParams:
     temperature: float = 0.7
@@ -28,8 +43,60 @@ class SamplingParams:
     # scheduling priority: waiting prompts of a higher priority are prefilled first
     # (an agent's post-tool re-prompt: its user has already waited through the call)
     priority: int = 0
+    # logit processors, applied to the raw logits in this order before the allow-mask,
+    # temperature, top-k and top-p (ops/reference.py apply_penalties):
+    # repetition (HF / vLLM ``repetition_penalty``, Ollama ``repeat_penalty``): a token of
+    # the prompt or the output so far has its logit divided (> 0) or multiplied (<= 0)
+    repetition_penalty: float = 1.0
+    # OpenAI: -= presence_penalty once / frequency_penalty per occurrence in the output
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    # OpenAI: token id (int or decimal str, as in the JSON) -> bias in [-100, 100]
+    logit_bias: Optional[dict] = None
+
+    MAX_LOGIT_BIAS = 300
+
+    @property
+    def has_penalties(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or \
+            self.frequency_penalty != 0.0 or bool(self.logit_bias)
+
+    def _check_penalties(self):
+        def num(name, default):
+            v = getattr(self, name)
+            if v is None:
+                v = default
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+                raise ValueError(f"{name} must be a number")
+            setattr(self, name, float(v))
+            return float(v)
+
+        if not num("repetition_penalty", 1.0) > 0.0 or self.repetition_penalty == float("inf"):
+            raise ValueError("repetition_penalty must be > 0")
+        for name in ("presence_penalty", "frequency_penalty"):
+            if not -2.0 <= num(name, 0.0) <= 2.0:
+                raise ValueError(f"{name} must be in [-2, 2]")
+        if self.logit_bias is None:
+            return
+        if not isinstance(self.logit_bias, dict):
+            raise ValueError("logit_bias must be a map of token id -> bias")
+        if len(self.logit_bias) > self.MAX_LOGIT_BIAS:
+            raise ValueError(f"logit_bias holds at most {self.MAX_LOGIT_BIAS} entries")
+        bias = {}
+        for k, v in self.logit_bias.items():
+            if isinstance(k, str) and k.strip().lstrip("+-").isdigit():
+                k = int(k.strip())
+            if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+                raise ValueError(f"logit_bias key {k!r} is not a token id")
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not -100.0 <= v <= 100.0:
+                raise ValueError(f"logit_bias[{k}] must be in [-100, 100]")
+            if k in bias:
+                raise ValueError(f"logit_bias names token {k} twice")
+            bias[k] = float(v)
+        self.logit_bias = bias or None
 
     def __post_init__(self):
+        self._check_penalties()
         if self.temperature is None:
             self.temperature = 0.7
         if self.temperature < 0:

@@ -302,8 +302,12 @@ class Scheduler:
         seq.pf_sched = 0
         seq.epoch += 1
 
-    def _schedule_prefill(self, budget: int, n_decode: int):
+    def _schedule_prefill(self, budget: int, n_decode: int, reserved: int = 0):
+        """``reserved``: sequences that count against ``max_num_seqs`` without being decode
+        rows of this step -- prompts completed by a queued mixed step that have not joined
+        ``running`` yet (engine ``_speculate_mixed``)."""
         seqs, ntok, samp, rejected = [], [], [], []
+        n_seqs = n_decode + reserved
         retried = None
         used = 0
         # the soft budget is for latency when the queue head is short (one turn of
@@ -318,7 +322,7 @@ class Scheduler:
             # the soft budget bounds the step's GEMM rows (decode rows + prefill
             # tokens), so a burst step stays inside the prefill GEMMs' 256-row tiles
             soft = max(self.bs, soft - n_decode)
-        while self.waiting and budget > 0 and n_decode + len(seqs) < self.max_num_seqs:
+        while self.waiting and budget > 0 and n_seqs + len(seqs) < self.max_num_seqs:
             if seqs and soft and used >= soft:
                 break
             seq = self.waiting[0]
@@ -377,7 +381,7 @@ class Scheduler:
             else:
                 break  # the partially prefilled prompt continues next step
         if self.background and not self.waiting and budget > 0 \
-                and n_decode + len(seqs) < self.max_num_seqs:
+                and n_seqs + len(seqs) < self.max_num_seqs:
             room = min(budget, soft - used) if soft else budget
             if room > 0:
                 self._schedule_background(room, seqs, ntok, samp, rejected)

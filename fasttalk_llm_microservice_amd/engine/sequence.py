@@ -39,7 +39,7 @@ class Sequence:
                  "first_token_time", "finish_reason", "detok_stream", "on_output", "grammar",
                  "grammar_state", "stop_buf", "text_len", "aborted", "preemptions", "admit_order",
                  "meta", "host_slots", "background", "jf_text", "jf_ids", "lazy", "inflight",
-                 "drop_next", "pf_sched", "epoch")
+                 "drop_next", "pf_sched", "epoch", "pen_slot")
 
     def __init__(self, request_id: str, prompt_ids: List[int], params: SamplingParams,
                  on_output: Optional[Callable[[RequestOutput], None]] = None, meta: Any = None):
@@ -87,6 +87,9 @@ class Sequence:
         # bumped when the sequence's KV is dropped (_reset_to_waiting): a queued
         # chunk scheduled before that is not counted when its step completes
         self.epoch = 0
+        # penalties: the sequence's slot of the runner's device state (engine free list);
+        # -1 = none (no penalties, not scheduled yet, preempted, or its grammar is bound)
+        self.pen_slot = -1
 
     # ---------------------------------------------------------------- tokens
     @property

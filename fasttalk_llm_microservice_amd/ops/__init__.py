@@ -367,6 +367,83 @@ def sample(logits, temperature, top_p, top_k, seeds, steps, out=None, mask=None)
     return r
 
 
+# ---------------------------------------------------------------------------------
+# penalties (repetition / presence / frequency / logit_bias): per-sequence device state
+# ---------------------------------------------------------------------------------
+
+PEN_MAX_BIAS = 300       # bias entries per slot (csrc/kernels/penalties.hip kPenMaxBias)
+PEN_PROMPT_BIT = 0x8000  # table entry: bit 15 = token is in the prompt
+PEN_COUNT_MAX = 0x7FFF   # bits 0-14 = saturating output count
+
+
+def penalty_state(slots: int, vocab: int, device):
+    """(table, bias_ids, bias_vals) of ``slots`` sequences: the table is int16 storage
+    of the uint16 entries [slots, vocab] (rows padded to 8 entries so each starts 16-B
+    aligned), the bias lists int32 / fp32 [slots, PEN_MAX_BIAS] (ids -1 = no entry)."""
+    vp = (vocab + 7) // 8 * 8
+    table = torch.zeros(slots, vp, dtype=torch.int16, device=device)[:, :vocab]
+    bias_ids = torch.full((slots, PEN_MAX_BIAS), -1, dtype=torch.int32, device=device)
+    bias_vals = torch.zeros(slots, PEN_MAX_BIAS, dtype=torch.float32, device=device)
+    return table, bias_ids, bias_vals
+
+
+def penalty_seed(table, slot: int, ids, vals, bias_ids, bias_vals, src_ids, src_vals):
+    """Clears row ``slot`` of the table, writes ``vals[i]`` (uint16 values as int32) at
+    the unique tokens ``ids[i]`` and installs the slot's bias list ``src_ids`` /
+    ``src_vals`` ([PEN_MAX_BIAS], ids -1 padded)."""
+    if table.is_cuda:
+        native().penalty_seed(table, int(slot), ids, vals, bias_ids, bias_vals, src_ids, src_vals)
+        return
+    v = table.shape[1]
+    idx = ids.long()
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= v):
+        raise IndexError("penalty_seed: token id out of range")
+    row = table[slot]
+    row.zero_()
+    row[idx] = torch.from_numpy(vals.numpy().astype(np.uint16).view(np.int16))
+    sid = src_ids.clone()
+    sid[(sid < 0) | (sid >= v)] = -1
+    bias_ids[slot] = sid
+    bias_vals[slot] = src_vals
+
+
+def penalty_update(table, slots, sampled):
+    """Saturating +1 on ``table[slots[r], sampled[r]]`` for rows with ``slots[r] >= 0``
+    (the rows of one step hold distinct slots)."""
+    if table.is_cuda:
+        native().penalty_update(table, slots, sampled)
+        return
+    for r, (s, t) in enumerate(zip(slots[: sampled.numel()].tolist(), sampled.tolist())):
+        if s < 0:
+            continue
+        e = int(table[s, t]) & 0xFFFF
+        if e & PEN_COUNT_MAX != PEN_COUNT_MAX:
+            table[s, t] = int(np.uint16(e + 1).view(np.int16))
+
+
+def penalty_apply(logits, slots, rep, pres, freq, table, bias_ids, bias_vals, out=None):
+    """Penalties and bias of rows with ``slots[r] >= 0`` (reference.apply_penalties over
+    the slot's table row and bias list); other rows are copied.  ``out`` None or the
+    logits themselves: in place."""
+    if out is None:
+        out = logits
+    if logits.is_cuda:
+        native().penalty_apply(logits, slots, rep, pres, freq, table, bias_ids, bias_vals, out)
+        return out
+    b = logits.shape[0]
+    sl = slots[:b].long()
+    rows = torch.nonzero(sl >= 0).flatten()
+    if out is not logits:
+        out.copy_(logits)
+    if rows.numel():
+        s = sl[rows]
+        e = table[s].to(torch.int32) & 0xFFFF
+        out[rows] = ref.apply_penalties(logits[rows], (e & PEN_PROMPT_BIT) != 0, e & PEN_COUNT_MAX,
+                                        rep[:b][rows], pres[:b][rows], freq[:b][rows],
+                                        bias_ids[s], bias_vals[s])
+    return out
+
+
 def kv_block_copy(k_cache, v_cache, pairs: torch.Tensor):
     if k_cache.is_cuda:
         native().kv_block_copy(k_cache, v_cache, pairs)

@@ -177,6 +177,45 @@ def paged_attention(q: torch.Tensor, k_cache, v_cache, block_tables, seq_lens, q
     return out
 
 
+def apply_penalties(logits: torch.Tensor, prompt_mask: torch.Tensor, counts: torch.Tensor,
+                    rep, pres, freq, bias_ids=None, bias_vals=None) -> torch.Tensor:
+    """Logit processors of the sampler (SamplingParams.repetition_penalty /
+    presence_penalty / frequency_penalty / logit_bias), the reference of
+    csrc/kernels/penalties.hip.  Per row, with raw logits ``l``, the set ``prompt_mask``
+    [B, V] (bool) of prompt tokens and the output counts ``counts`` [B, V]:
+
+    1. repetition (prompt and output tokens): ``l = l / rep if l > 0 else l * rep``
+    2. frequency / presence (output tokens): ``l -= freq * c + pres * (c > 0)``
+    3. bias: ``l[bias_ids] += bias_vals`` (``bias_ids`` [B, K], -1 = no entry)
+
+    ``rep`` / ``pres`` / ``freq``: [B].  fp32 throughout, each operation rounded on its
+    own, one rounding to the logits' dtype at the end; an element that is in no set and
+    has no bias keeps its input bits."""
+    x = logits.float()
+    b, v = x.shape
+    f32 = dict(dtype=torch.float32, device=x.device)
+    rep = torch.as_tensor(rep, **f32).reshape(b, 1)
+    pres = torch.as_tensor(pres, **f32).reshape(b, 1)
+    freq = torch.as_tensor(freq, **f32).reshape(b, 1)
+    c = counts.to(torch.float32)
+    seen = prompt_mask.bool() | (counts > 0)
+    y = torch.where(x > 0, x / rep, x * rep)
+    y = y - (freq * c + torch.where(counts > 0, pres, torch.zeros_like(pres)))
+    y = torch.where(seen, y, x)
+    touched = seen
+    if bias_ids is not None and bias_ids.numel():
+        ids = bias_ids.to(torch.int64)
+        valid = ids >= 0
+        add = torch.zeros_like(y)
+        hit = torch.zeros_like(seen)
+        rows = torch.arange(b, device=x.device).view(b, 1).expand_as(ids)
+        add[rows[valid], ids[valid]] = bias_vals.to(torch.float32)[valid]
+        hit[rows[valid], ids[valid]] = True
+        y = torch.where(hit, y + add, y)
+        touched = touched | hit
+    return torch.where(touched, y.to(logits.dtype), logits)
+
+
 def sample(logits: torch.Tensor, temperature, top_p, top_k, seeds, steps,
            mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Reference sampler (CPU backend).  Same contract as the HIP kernel:
