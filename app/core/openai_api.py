@@ -58,22 +58,52 @@ def register_openai_routes(app, handler) -> None:
                   seed=body.get("seed"), ignore_eos=bool(body.get("ignore_eos", False)),
                   min_tokens=int(body.get("min_tokens") or 0))
         # presence_penalty / frequency_penalty / logit_bias, and vLLM's repetition_penalty
-        from fasttalk_llm_microservice_amd.engine.sampling_params import pick_penalties
+        from fasttalk_llm_microservice_amd.engine.sampling_params import (pick_logprobs,
+                                                                           pick_penalties)
+
+        def bad_request(msg: str):
+            return JSONResponse({"error": {"message": msg, "type": "invalid_request_error"}},
+                                status_code=400)
 
         try:
             kw["penalties"] = pick_penalties(body) or None
+            want_lp = pick_logprobs(body)
         except (ValueError, TypeError) as e:
-            return JSONResponse({"error": {"message": str(e), "type": "invalid_request_error"}},
-                                status_code=400)
+            return bad_request(str(e))
+        if want_lp is not None:
+            # logprobs / top_logprobs: per-token logprobs over the raw logits.  Not with a
+            # grammar (forced tokens have no sampled logit) nor tool parsing, nor under TP.
+            if tools or guided is not None:
+                return bad_request("logprobs are not supported with tools or response_format "
+                                   "json_schema")
+            inner = getattr(handler.engine, "engine", handler.engine)
+            if int(getattr(getattr(inner, "cfg", None), "tp_size", 1) or 1) > 1:
+                return bad_request("logprobs are not supported with tensor parallelism yet")
+            kw["logprobs"] = want_lp
+        tok_bytes = handler.tokenizer.id_to_bytes if want_lp is not None else None
+
+        def lp_item(tid: int, lp: float) -> Dict[str, Any]:
+            b = tok_bytes[tid] if 0 <= tid < len(tok_bytes) else b""
+            # JSON has no infinity: -inf goes out as -9999.0 (vLLM's convention)
+            return {"token": b.decode("utf-8", errors="replace"),
+                    "logprob": lp if lp > -9999.0 else -9999.0, "bytes": list(b)}
+
+        def lp_content(entries) -> List[Dict[str, Any]]:
+            """OpenAI ``logprobs.content`` items of an event's RequestOutput.logprobs."""
+            return [dict(lp_item(tid, lp), top_logprobs=[lp_item(a, alp) for a, alp in alts])
+                    for tid, lp, alts in entries or ()]
+
         rid = f"chatcmpl-{uuid.uuid4().hex[:24]}"
         created = int(time.time())
         model = body.get("model") or handler.model
 
-        def chunk(delta: Dict[str, Any], finish=None) -> str:
+        def chunk(delta: Dict[str, Any], finish=None, lps=None) -> str:
+            choice = {"index": 0, "delta": delta, "finish_reason": finish}
+            if lps is not None:
+                choice["logprobs"] = {"content": lps}
             return "data: " + json.dumps({"id": rid, "object": "chat.completion.chunk",
                                           "created": created, "model": model,
-                                          "choices": [{"index": 0, "delta": delta,
-                                                       "finish_reason": finish}]}) + "\n\n"
+                                          "choices": [choice]}) + "\n\n"
 
         if body.get("stream"):
             async def gen():
@@ -88,13 +118,22 @@ def register_openai_routes(app, handler) -> None:
                 tcp = StreamingToolCallParser(names) if tools else None
                 any_call = False
                 tool_text = []   # what the parser consumed, re-sent as content if no call
+                # logprob entries not sent yet: an event without text (partial UTF-8) sends
+                # no chunk, its entries go out with the next chunk or the final one
+                held: List[Dict[str, Any]] = []
                 async for out in handler.stream_events(messages, request_id=rid, **kw):
                     if out.finished:
                         finish = out.finish_reason
+                    if want_lp is not None:
+                        held += lp_content(out.logprobs)
                     if not out.text:
                         continue
                     if det is None:
-                        yield chunk({"content": out.text})
+                        if want_lp is not None:
+                            yield chunk({"content": out.text}, lps=held)
+                            held = []
+                        else:
+                            yield chunk({"content": out.text})
                         continue
                     mode, emit = det.feed(out.text)
                     if mode == "text":
@@ -115,7 +154,8 @@ def register_openai_routes(app, handler) -> None:
                     yield chunk({"content": "".join(tool_text)})
                 if any_call:
                     finish = "tool_calls"
-                yield chunk({}, finish if finish in ("stop", "length", "tool_calls") else "stop")
+                yield chunk({}, finish if finish in ("stop", "length", "tool_calls") else "stop",
+                            lps=held or None)
                 yield "data: [DONE]\n\n"
 
             return StreamingResponse(gen(), media_type="text/event-stream")
@@ -123,9 +163,12 @@ def register_openai_routes(app, handler) -> None:
         parts: List[str] = []
         n_prompt = n_out = 0
         finish = "stop"
+        lp_all: List[Dict[str, Any]] = []
         async for out in handler.stream_events(messages, request_id=rid, **kw):
             parts.append(out.text)
             n_out += len(out.token_ids)
+            if want_lp is not None:
+                lp_all += lp_content(out.logprobs)
             n_prompt = out.num_prompt_tokens or n_prompt
             if out.finished:
                 finish = out.finish_reason
@@ -138,8 +181,11 @@ def register_openai_routes(app, handler) -> None:
                 msg = {"role": "assistant", "content": rest or None,
                        "tool_calls": [c.to_openai() for c in calls]}
                 finish = "tool_calls"
+        choice = {"index": 0, "message": msg,
+                  "finish_reason": finish if finish in ("stop", "length", "tool_calls") else "stop"}
+        if want_lp is not None:
+            choice["logprobs"] = {"content": lp_all}
         return {"id": rid, "object": "chat.completion", "created": created, "model": model,
-                "choices": [{"index": 0, "message": msg,
-                             "finish_reason": finish if finish in ("stop", "length", "tool_calls") else "stop"}],
+                "choices": [choice],
                 "usage": {"prompt_tokens": n_prompt, "completion_tokens": n_out,
                           "total_tokens": n_prompt + n_out}}

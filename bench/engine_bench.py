@@ -29,6 +29,8 @@ def main():
     # sampler penalties on every row (the decode graph then runs apply -> sample -> update)
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
     ap.add_argument("--frequency-penalty", type=float, default=0.0)
+    # per-token logprobs with N alternatives on every row (ops.logprobs behind every sampler)
+    ap.add_argument("--logprobs", type=int, default=None)
     a = ap.parse_args()
 
     import numpy as np
@@ -49,7 +51,7 @@ def main():
         prompts = [rng.integers(0, 120000, a.prompt).tolist() for _ in range(a.seqs)]
         sp = SamplingParams(temperature=a.temperature, top_p=0.9, max_tokens=a.gen, ignore_eos=True,
                             repetition_penalty=a.repetition_penalty,
-                            frequency_penalty=a.frequency_penalty)
+                            frequency_penalty=a.frequency_penalty, logprobs=a.logprobs)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i, p in enumerate(prompts):
@@ -67,7 +69,7 @@ def main():
         res.append({"round": r, "tokens": ntok, "seconds": dt, "tok_s": ntok / dt,
                     "ttft_s": first, "decode_step_ms": m["decode_step_ms_avg"],
                     "prefill_step_ms": m["prefill_step_ms_avg"],
-                    "penalty_steps": m["penalty_steps"]})
+                    "penalty_steps": m["penalty_steps"], "logprob_steps": m["logprob_steps"]})
         print(json.dumps(res[-1]), flush=True)
     print(json.dumps({"final": res[-1], "runner": eng.runner.stats}), flush=True)
 

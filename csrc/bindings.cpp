@@ -41,6 +41,10 @@ int ft_sample(int* out_tokens, const void* logits, int logits_is_bf16, long logi
               const int* top_k, const long long* seeds, const int* steps,
               const uint32_t* allow_mask, int mask_words, float* ws, hipStream_t stream);
 int ft_sample_ws_floats();
+int ft_logprobs_max();
+int ft_logprobs_ws_words();
+int ft_logprobs(const void* logits, int is_bf16, long stride, int rows, int vocab, const int* sampled,
+                const int* want, void* ws, float* out_lp, int* out_id, hipStream_t stream);
 int ft_penalty_max_bias();
 int ft_penalty_apply(const void* logits, void* out, int is_bf16, long lstride, long ostride, int rows,
                      int vocab, const int* slots, const float* rep, const float* pres,
@@ -480,6 +484,38 @@ void penalty_seed(at::Tensor table, int64_t slot, at::Tensor ids, at::Tensor val
                            bias_vals.data_ptr<float>(), src_ids.data_ptr<int>(),
                            src_vals.data_ptr<float>(), cur_stream()),
            "penalty_seed");
+}
+
+// logprobs (csrc/kernels/logprobs.hip): raw logits [B, V] (row stride a multiple of 8, V
+// any), sampled / want int32 [>= B], out_lp fp32 / out_id int32 [>= B, 1 + 20] contiguous
+void logprobs(at::Tensor logits, at::Tensor sampled, at::Tensor want, at::Tensor out_lp,
+              at::Tensor out_id) {
+  check_dev(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits [B, V] with contiguous rows");
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(is_bf16 || logits.scalar_type() == at::kFloat, "logits fp32 or bf16");
+  const int rows = (int)logits.size(0), vocab = (int)logits.size(1);
+  TORCH_CHECK((rows <= 1 || logits.stride(0) % 8 == 0) &&
+                  reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "logits rows must start 16-B aligned (row stride a multiple of 8)");
+  check_i32(sampled, "sampled");
+  check_i32(want, "want");
+  TORCH_CHECK(sampled.numel() >= rows && want.numel() >= rows, "sampled / want length");
+  const int64_t cols = 1 + ft_logprobs_max();
+  check_dev(out_lp, "out_lp");
+  check_i32(out_id, "out_id");
+  TORCH_CHECK(out_lp.scalar_type() == at::kFloat && out_lp.is_contiguous() && out_lp.dim() == 2 &&
+                  out_id.dim() == 2 && out_lp.size(1) == cols && out_id.size(1) == cols &&
+                  out_lp.size(0) >= rows && out_id.size(0) >= rows,
+              "out_lp fp32 / out_id int32 [B, ", cols, "]");
+  at::Tensor ws = at::empty({(int64_t)rows * ft_logprobs_ws_words()},
+                            logits.options().dtype(at::kLong));   // stream-ordered scratch
+  // a single row's stride is arbitrary (and unused): hand the launcher a valid one
+  const long stride = rows > 1 ? (long)logits.stride(0) : (long)((vocab + 7) / 8 * 8);
+  check_rc(ft_logprobs(logits.data_ptr(), is_bf16 ? 1 : 0, stride, rows, vocab,
+                       sampled.data_ptr<int>(), want.data_ptr<int>(), ws.data_ptr(),
+                       out_lp.data_ptr<float>(), out_id.data_ptr<int>(), cur_stream()),
+           "logprobs");
 }
 
 void kv_block_copy(at::Tensor k_cache, at::Tensor v_cache, at::Tensor src_dst) {
@@ -1054,6 +1090,7 @@ FT_HOOK_DECL(norm_act)
 FT_HOOK_DECL(sampling)
 FT_HOOK_DECL(kv_copy)
 FT_HOOK_DECL(penalties)
+FT_HOOK_DECL(logprobs)
 #undef FT_HOOK_DECL
 }
 
@@ -1066,7 +1103,8 @@ void set_kernel_checks(torch::Tensor word) {
   const Hook hooks[] = {ft_check_hook_attn_decode, ft_check_hook_attn_prefill,
                         ft_check_hook_rope_kv,     ft_check_hook_fused_epilogue,
                         ft_check_hook_norm_act,    ft_check_hook_sampling,
-                        ft_check_hook_kv_copy,     ft_check_hook_penalties};
+                        ft_check_hook_kv_copy,     ft_check_hook_penalties,
+                        ft_check_hook_logprobs};
   for (Hook h : hooks) check_rc(h(w), "set_kernel_checks");
 }
 #endif
@@ -1110,6 +1148,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("penalty_update", &penalty_update);
   m.def("penalty_seed", &penalty_seed);
   m.def("penalty_max_bias", []() { return (int64_t)ft_penalty_max_bias(); });
+  m.def("logprobs", &logprobs);
+  m.def("logprobs_max", []() { return (int64_t)ft_logprobs_max(); });
   m.def("kv_block_copy", &kv_block_copy);
   m.def("kv_swap", &kv_swap, py::arg("ptrs"), py::arg("ids"), py::arg("staging"),
         py::arg("block_elems"), py::arg("to_staging"), py::arg("num_blocks") = 0);

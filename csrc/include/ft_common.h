@@ -183,6 +183,7 @@ enum FtCheckCode : int {
   kCkCopyBlock = 6,    // KV copy / swap: block id >= num_blocks
   kCkPenSlot = 7,      // penalties: state slot >= max_num_seqs
   kCkPenToken = 8,     // penalties: sampled / seeded / biased token id >= vocab
+  kCkLogprobWant = 9,  // logprobs: a row's number of alternatives > 20
 };
 }  // namespace ft
 

@@ -138,6 +138,9 @@ class LLMEngine:
         self._pen_free: List[int] = list(range(n_pen - 1, -1, -1))
         self._pen_owner: Dict[int, Sequence] = {}
         self._pen_reqs: set = set()
+        # unfinished requests with SamplingParams.logprobs (runner.lp_active: steps scan
+        # their rows for it only while there is one)
+        self._lp_reqs: set = set()
         # FT_PENALTY_VERIFY=1 (tests, debugging): a finishing sequence's slot is read back
         # and compared with the host's truth (_pen_verify)
         self.pen_verify = os.environ.get("FT_PENALTY_VERIFY", "0") == "1"
@@ -159,9 +162,14 @@ class LLMEngine:
                               f"{self.max_model_len}")
         if params.has_penalties:
             self._check_penalties(params)
+        if params.logprobs is not None:
+            self._check_logprobs(params)
         seq = Sequence(request_id, prompt_ids, params, on_output, meta)
         if params.has_penalties:
             self._pen_reqs.add(request_id)
+        if params.logprobs is not None:
+            self._lp_reqs.add(request_id)
+            self.runner.lp_active = True
         seq.background = bool(background)
         if self._trace_path:
             self._trace.append(("arrive", time.perf_counter(), len(prompt_ids)))
@@ -205,6 +213,17 @@ class LLMEngine:
         for t in (params.logit_bias or ()):
             if not 0 <= t < vocab:
                 raise ValueError(f"logit_bias token id {t} is outside the vocabulary [0, {vocab})")
+
+    def _check_logprobs(self, params: SamplingParams):
+        """SamplingParams.logprobs: per-token logprobs over the raw logits, computed by the
+        step that samples the token (runner._lp_launch) and handed to _process_token."""
+        if self.cfg.tp_size > 1:
+            raise EngineError("logprobs are not supported with tensor parallelism yet")
+        if params.guided is not None:
+            # jump-forward tokens and dropped samples have no sampled logit
+            raise EngineError("logprobs are not supported with guided decoding")
+        if not hasattr(self.runner, "take_logprobs"):
+            raise EngineError("logprobs are not supported by this runner")
 
     @staticmethod
     def _pen_wants(q: Sequence) -> bool:
@@ -560,12 +579,13 @@ class LLMEngine:
             self._drain_wait(e)
         tl = time.perf_counter()
         toks = self.runner.mixed_collect(handle) if e.mixed else self.runner.decode_collect(handle)
+        lps = self.runner.take_logprobs(handle) if self._lp_reqs else None
         t1 = time.perf_counter()
         self._inflight.pop(0)
         sampled = batch.sampled_seqs()
         for q in sampled:
             q.inflight -= 1
-        outs = self._complete(batch, sampled, toks)
+        outs = self._complete(batch, sampled, toks, lps)
         # the guided step queued behind this one: its forward pass is running; its
         # sampler goes in now that this step's tokens have moved the grammars
         if self._inflight and getattr(self._inflight[0].handle, "pending", False):
@@ -594,15 +614,16 @@ class LLMEngine:
         hp["steps"] += 1
         return outs
 
-    def _complete(self, batch: ScheduledBatch, sampled_seqs, toks) -> List[RequestOutput]:
+    def _complete(self, batch: ScheduledBatch, sampled_seqs, toks, lps=None) -> List[RequestOutput]:
+        """``lps``: the step's per-row logprob entries (runner.take_logprobs) or None."""
         outs: List[RequestOutput] = []
         self.scheduler.post_step(batch)
-        for seq, tok in zip(sampled_seqs, toks):
+        for i, (seq, tok) in enumerate(zip(sampled_seqs, toks)):
             if seq.drop_next:   # its forced tokens replaced this sample (jump-forward)
                 seq.drop_next -= 1
                 self.stats["pipelined_jump_drops"] += 1
                 continue
-            o = self._process_token(seq, int(tok))
+            o = self._process_token(seq, int(tok), lps[i] if lps is not None else None)
             if o is not None:
                 outs.append(o)
         self.stats["generated_tokens"] += len(sampled_seqs)
@@ -720,11 +741,12 @@ class LLMEngine:
             return self._step_pipelined()
         self._executing = batch
         toks = self.runner.execute(batch, masks)
+        lps = self.runner.take_logprobs() if self._lp_reqs else None
         self._executing = None
         t1 = time.perf_counter()
         self.scheduler.post_step(batch)
-        for seq, tok in zip(sampled_seqs, toks):
-            o = self._process_token(seq, int(tok))
+        for i, (seq, tok) in enumerate(zip(sampled_seqs, toks)):
+            o = self._process_token(seq, int(tok), lps[i] if lps is not None else None)
             if o is not None:
                 outs.append(o)
         t2 = time.perf_counter()
@@ -789,10 +811,14 @@ class LLMEngine:
             self.stats["jump_forward_tokens"] += len(used)
         return text, used
 
-    def _process_token(self, seq: Sequence, tok: int) -> Optional[RequestOutput]:
+    def _process_token(self, seq: Sequence, tok: int, lp=None) -> Optional[RequestOutput]:
+        """``lp``: the token's logprob entry from the step that sampled it
+        (``(token_id, logprob, alternatives)``; requests with SamplingParams.logprobs)."""
         if seq.status == SeqStatus.FINISHED:
             return None
         p = seq.params
+        if p.logprobs is not None and (lp is None or lp[0] != tok):
+            raise EngineError(f"{seq.request_id}: the step returned no logprobs for token {tok}")
         now = time.perf_counter()
         first = seq.first_token_time is None
         if first:
@@ -854,17 +880,21 @@ class LLMEngine:
                 reason = "stop"
         elif p.stop and reason is not None:
             pass
-        ids = pre_ids + ([] if (is_stop_tok and reason == "stop") else [tok]) + post_ids
+        dropped = is_stop_tok and reason == "stop"   # the stop token that ends a reply
+        ids = pre_ids + ([] if dropped else [tok]) + post_ids
+        # aligned with ids (requests with logprobs carry no grammar: no forced ids)
+        lps = None if p.logprobs is None else ([] if dropped else [lp])
         if reason is not None:
-            return self._finalize(seq, reason, emit=True, delta=delta, ids=ids)
+            return self._finalize(seq, reason, emit=True, delta=delta, ids=ids, lps=lps)
         if not delta and not first:
             # nothing printable yet (partial UTF-8): still report progress
-            out = RequestOutput(seq.request_id, "", ids, num_output_tokens=n_out)
+            out = RequestOutput(seq.request_id, "", ids, num_output_tokens=n_out, logprobs=lps)
         else:
             out = RequestOutput(seq.request_id, delta, ids, num_output_tokens=n_out,
                                 num_prompt_tokens=seq.prompt_len,
                                 num_cached_tokens=seq.num_cached_tokens,
-                                ttft_s=(seq.first_token_time - seq.arrival) if first else None)
+                                ttft_s=(seq.first_token_time - seq.arrival) if first else None,
+                                logprobs=lps)
         if seq.on_output is not None:
             seq.on_output(out)
         return out
@@ -893,10 +923,14 @@ class LLMEngine:
         return buf[: len(buf) - hold], False
 
     def _finalize(self, seq: Sequence, reason: str, emit: bool, delta: str = "",
-                  ids: Optional[List[int]] = None, error: Optional[str] = None) -> RequestOutput:
+                  ids: Optional[List[int]] = None, error: Optional[str] = None,
+                  lps: Optional[list] = None) -> RequestOutput:
         if seq.status != SeqStatus.FINISHED or seq.block_ids:
             self.scheduler.finish(seq, reason)
         seq.finish_reason = reason
+        if self._lp_reqs:
+            self._lp_reqs.discard(seq.request_id)
+            self.runner.lp_active = bool(self._lp_reqs)
         if seq.pen_slot >= 0:
             try:
                 if self.pen_verify and reason != "error":
@@ -924,7 +958,8 @@ class LLMEngine:
         out = RequestOutput(seq.request_id, text, ids or [], finished=True, finish_reason=reason,
                             num_prompt_tokens=seq.prompt_len,
                             num_cached_tokens=seq.num_cached_tokens,
-                            num_output_tokens=seq.num_output, error=error)
+                            num_output_tokens=seq.num_output, error=error,
+                            logprobs=None if seq.params.logprobs is None else (lps or []))
         self.stats["finished_" + reason] += 1
         if emit and seq.on_output is not None:
             seq.on_output(out)
@@ -1007,6 +1042,8 @@ class LLMEngine:
             "guided_capped_steps": self.scheduler.guided_capped,
             "penalty_slots_in_use": len(self._pen_owner),
             "penalty_steps": int(getattr(self.runner, "stats", {}).get("penalty_steps", 0)),
+            "logprob_steps": int(getattr(self.runner, "stats", {}).get("logprob_steps", 0)),
+            "logprob_rows": int(getattr(self.runner, "stats", {}).get("logprob_rows", 0)),
             "swapped": len(self.scheduler.swapped),
             "swap_outs": self.scheduler.num_swap_out,
             "swap_ins": self.scheduler.num_swap_in,

@@ -41,7 +41,8 @@ class KernelCheckError(RuntimeError):
     CODES = {1: "block-table entry >= num_blocks", 2: "KV slot >= pool capacity",
              3: "position >= rotary table rows", 4: "input token id >= vocab",
              5: "sampled token id >= vocab", 6: "KV copy/swap block id >= num_blocks",
-             7: "penalty slot >= max_num_seqs", 8: "penalty token id >= vocab"}
+             7: "penalty slot >= max_num_seqs", 8: "penalty token id >= vocab",
+             9: "logprob alternatives > 20"}
 
     def __init__(self, word):
         count, code, ctx, value = (int(x) for x in word[:4])
@@ -142,12 +143,55 @@ class _Uploader:
         return outs
 
 
+class _LpHost:
+    """Pinned host side of a step's per-token logprobs (SamplingParams.logprobs): the
+    rows' ``want`` going up (-1 = the row did not ask) and the kernel's two result
+    arrays [rows, 1 + 20] coming back.  ``n``: rows of the step it holds results of (0:
+    none -- no row of the step asked)."""
+    __slots__ = ("want", "lp", "ids", "n", "pin")
+
+    def __init__(self, rows: int, pin: bool):
+        self.pin = pin
+        self.n = 0
+        self._alloc(rows)
+
+    def _alloc(self, rows: int):
+        cols = 1 + ops.LOGPROBS_MAX
+        self.want = torch.full((rows,), -1, dtype=torch.int32, pin_memory=self.pin)
+        self.lp = torch.zeros(rows, cols, dtype=torch.float32, pin_memory=self.pin)
+        self.ids = torch.zeros(rows, cols, dtype=torch.int32, pin_memory=self.pin)
+
+    def stage(self, want: np.ndarray) -> int:
+        n = len(want)
+        if self.want.shape[0] < n:
+            self._alloc(2 * n)
+        self.want.numpy()[:n] = want
+        self.n = n
+        return n
+
+    def take(self) -> Optional[list]:
+        """Per row ``(token_id, logprob, [(alt_id, alt_logprob), ...])`` or None (the row
+        did not ask); None when the step computed none.  Read after the step's event."""
+        n, self.n = self.n, 0
+        if not n:
+            return None
+        want = self.want.numpy()[:n].tolist()
+        lp = self.lp.numpy()[:n].tolist()
+        ids = self.ids.numpy()[:n].tolist()
+        return [None if w < 0 else (ids[r][0], lp[r][0], list(zip(ids[r][1:1 + w], lp[r][1:1 + w])))
+                for r, w in enumerate(want)]
+
+
 class _Staging:
     """Pinned host mirror of the decode graph's device inputs + its output copy.
     int32 ``small`` fields: ids | pos | slots | seq_lens | top_k | steps."""
 
     def __init__(self, mb: int, max_blocks: int, pin: bool, gpu: bool):
         i32 = torch.int32
+        # per-token logprobs: a pinned buffer of its own (not part of h_all, whose layout
+        # and upload size stay as they are); lp_want: the staged step's array or None
+        self.lp = _LpHost(mb, pin)
+        self.lp_want: Optional[np.ndarray] = None
         # one pinned int32 image, laid out like the device inputs (_input_views), so a
         # step's inputs go up in ONE copy: small | f32 | seeds (int64) | block tables
         pw = pen_words(mb)
@@ -175,10 +219,11 @@ class MixedHandle:
     builds the step queued behind it once the GPU passes it).  They rotate; a
     handle is reused only after MIXED_HANDLES - 1 later mixed launches, more than
     the steps the engine keeps queued (ENGINE_PIPELINE_DEPTH + 1)."""
-    __slots__ = ("host", "event", "mark", "n", "pending", "logits", "samp", "seqs")
+    __slots__ = ("host", "event", "mark", "n", "pending", "logits", "samp", "seqs", "lp")
 
     def __init__(self, rows: int, pin: bool, gpu: bool):
         self.host = torch.zeros(rows, dtype=torch.int32, pin_memory=pin)
+        self.lp = _LpHost(rows, pin)   # per-token logprobs of the step it holds
         self.event = torch.cuda.Event() if gpu else None
         self.mark = torch.cuda.Event() if gpu else None
         self.n = 0
@@ -350,6 +395,16 @@ class ModelRunner:
         self._upload = _Uploader(dv, pin) if self.is_gpu else None
         self.h_out = torch.zeros(mb, dtype=i32, pin_memory=pin)  # eager-step sampler output
         self.h_err = torch.zeros(1, dtype=i32, pin_memory=pin)
+        # per-token logprobs (ops.logprobs, launched eagerly behind the sampler of steps in
+        # which some row asked): the device side of a step's want / result arrays -- one
+        # set: a step's results are copied out in stream order before the next launch
+        # overwrites them -- and the pinned host side of synchronous eager steps
+        self.lp_active = False   # the engine holds an unfinished request with logprobs
+        self.d_lp_want = torch.full((mb,), -1, dtype=i32, device=dv)
+        self.d_lp = torch.zeros(mb, 1 + ops.LOGPROBS_MAX, dtype=torch.float32, device=dv)
+        self.d_lp_ids = torch.zeros(mb, 1 + ops.LOGPROBS_MAX, dtype=i32, device=dv)
+        self._lp_sync = _LpHost(mb, pin)
+        self._lp_last = self._lp_sync   # where the last synchronous step's results are
         # TP rank 0 decides about collective faults; workers only follow its messages
         self.checks_comm = comm.world_size > 1 and comm.rank == 0
         # guided decoding (E19): the token allow-mask is a STATIC input of every
@@ -431,7 +486,7 @@ class ModelRunner:
             if comm.world_size > 1 else 0
         self._trace_tp = os.environ.get("FT_TP_TRACE", "0") == "1" and comm.world_size > 1
         self.stats = {"graph_replays": 0, "eager_decode": 0, "prefill_steps": 0, "captures": 0,
-                      "penalty_steps": 0}
+                      "penalty_steps": 0, "logprob_steps": 0, "logprob_rows": 0}
         # tests: a list here collects every step's logits (fp32; eager steps on the host,
         # graph-replayed and mixed-ahead steps as stream-ordered device copies) -- TP-vs-TP=1
         # numerics are compared on logits, not on greedy tokens of random weights.  With
@@ -640,6 +695,52 @@ class ModelRunner:
         ops.penalty_update(self.pen_table, slot, out[:logits.shape[0]])
         return out
 
+    # ------------------------------------------------------------------ per-token logprobs
+    # A logprob belongs to the step that sampled its token: nothing is kept between
+    # steps.  A step in which some row asked launches ops.logprobs eagerly on the
+    # step's stream right behind its sampler -- over the RAW logits (never
+    # penalty_apply's output) and the sampled ids -- and copies the two result arrays
+    # into the step's pinned _LpHost before the step's event is recorded, so the
+    # collect finds them complete when the tokens are.  The decode graphs are not
+    # touched; a step in which no row asked launches and uploads nothing new.
+    def _lp_arrays(self, seqs) -> Optional[np.ndarray]:
+        """``want`` (int32 per sampled row: alternatives asked, -1 = none) of a step, or
+        None when no row asked."""
+        if not self.lp_active:
+            return None
+        want = None
+        for i, s in enumerate(seqs):
+            k = s.params.logprobs
+            if k is None:
+                continue
+            if want is None:
+                want = np.full(len(seqs), -1, np.int32)
+            want[i] = k
+        return want
+
+    def _lp_launch(self, hb: "_LpHost", want: np.ndarray, logits, sampled):
+        """Queues the logprobs of a step: ``want`` up, the kernel over the raw ``logits``
+        rows and their ``sampled`` ids, the results down into ``hb``."""
+        n = hb.stage(want)
+        if self.d_lp_want.shape[0] < n:   # (eager steps may sample more rows than a graph holds)
+            dv, cols = self.device, 1 + ops.LOGPROBS_MAX
+            self.d_lp_want = torch.full((2 * n,), -1, dtype=torch.int32, device=dv)
+            self.d_lp = torch.zeros(2 * n, cols, dtype=torch.float32, device=dv)
+            self.d_lp_ids = torch.zeros(2 * n, cols, dtype=torch.int32, device=dv)
+        dw, dl, di = self.d_lp_want[:n], self.d_lp[:n], self.d_lp_ids[:n]
+        dw.copy_(hb.want[:n], non_blocking=True)
+        ops.logprobs(logits[:n], sampled[:n], dw, dl, di)
+        hb.lp[:n].copy_(dl, non_blocking=True)
+        hb.ids[:n].copy_(di, non_blocking=True)
+        self.stats["logprob_steps"] += 1
+        self.stats["logprob_rows"] += int((want >= 0).sum())
+
+    def take_logprobs(self, h=None) -> Optional[list]:
+        """The per-row logprob entries of a collected step (``h``: its handle; None: the
+        synchronous step ``execute`` just ran), or None when no row of it asked."""
+        hb = self._lp_last if h is None else (h.stage.lp if isinstance(h, DecodeHandle) else h.lp)
+        return hb.take()
+
     def _mixed(self, batch: ScheduledBatch, masks) -> List[int]:
         host = self._mixed_host(batch)
         if self.bcast is not None:
@@ -710,6 +811,7 @@ class ModelRunner:
         sseqs = dseqs + [s for s, sm in zip(pseqs, psamp) if sm]
         host["sampling"] = self._sampling_arrays(sseqs)
         host["pen"] = self._pen_arrays(sseqs)
+        host["lp"] = self._lp_arrays(sseqs)
         if self.logits_tap_ids is not None:
             self._tap_rows = [s.request_id for s in sseqs]
         return host
@@ -784,7 +886,7 @@ class ModelRunner:
         dmask = dev[k + 5] if masks is not None else None
         dpen = dev[-4:] if pen is not None else None
         return self._sample(h, host["sampling"], masks, dev_sampling=samp, dev_mask=dmask,
-                            dev_pen=dpen)
+                            dev_pen=dpen, lp_want=host.get("lp"))
 
     def _wait(self, ev=None):
         """Block until the GPU work queued so far (or up to ``ev``) is done WITHOUT
@@ -843,8 +945,11 @@ class ModelRunner:
         if self.d_check is not None:
             self.d_check.zero_()
 
-    def _sample(self, h, sampling, masks, dev_sampling=None, dev_mask=None, dev_pen=None) -> List[int]:
+    def _sample(self, h, sampling, masks, dev_sampling=None, dev_mask=None, dev_pen=None,
+                lp_want=None) -> List[int]:
         logits = self.model.compute_logits(h)
+        self._lp_sync.n = 0
+        self._lp_last = self._lp_sync
         if self.logits_tap is not None:
             self._tap(logits.float().cpu())
         if dev_sampling is None:
@@ -856,6 +961,8 @@ class ModelRunner:
             dev_sampling = dev[:5]
             dev_mask = dev[5] if masks is not None else None
         out = self._pen_sample(logits, dev_sampling, dev_mask, dev_pen)
+        if lp_want is not None:
+            self._lp_launch(self._lp_sync, lp_want, logits, out)
         if not self.is_gpu:
             return out.tolist()
         n = out.shape[0]
@@ -921,7 +1028,9 @@ class ModelRunner:
         bucket = self._bucket(n) if self.use_graphs else None
         if bucket is None:
             return self._decode_eager(seqs, masks)
-        return self.decode_collect(self.decode_launch(seqs, masks=masks))
+        h = self.decode_launch(seqs, masks=masks)
+        self._lp_last = h.stage.lp
+        return self.decode_collect(h)
 
     def can_pipeline(self, n: int) -> bool:
         return self.use_graphs and self._bucket(n) is not None
@@ -954,6 +1063,10 @@ class ModelRunner:
         st.pen = pa is not None
         if pa is not None:
             self._pen_stage(st, pa, n, nb)
+        # logprobs: launched behind the sampler, wherever that is queued (a deferred
+        # sampler reads its rows again in sample_launch)
+        st.lp.n = 0
+        st.lp_want = None if defer_sample else self._lp_arrays(seqs)
         gather = None
         if ahead and rowmap is not None:
             gather = np.zeros(nb, dtype=np.int64)   # padding rows read row 0 (ignored)
@@ -996,7 +1109,8 @@ class ModelRunner:
                 dev = self._upload(arrays) if self.is_gpu else \
                     [torch.from_numpy(np.ascontiguousarray(a)) for a in arrays]
             dmask = dev[0] if masks is not None else None
-            self._mixed_sample(h, h.logits, h.samp, dmask, dev[-4:] if pen is not None else None)
+            self._mixed_sample(h, h.logits, h.samp, dmask, dev[-4:] if pen is not None else None,
+                               self._lp_arrays(h.seqs) if h.seqs is not None else None)
             return
         assert h.pending and self._pending_split is h
         self._set_masks(masks, h.n)
@@ -1013,6 +1127,13 @@ class ModelRunner:
         pair = self.graphs_split.get(key) or self._capture_split(h.nb, pen is not None)
         pair[1].replay()
         self._pending_split = None
+        want = self._lp_arrays(h.seqs) if h.seqs is not None else None
+        if want is not None:   # before anything else can replay over the forward's logits
+            self._lp_launch(st.lp, want, self._fwd_logits[h.nb], self.d_out)
+        if self.logits_tap is not None and h.seqs is not None:
+            if self.logits_tap_ids is not None:
+                self._tap_rows = [s.request_id for s in h.seqs]
+            self._tap(self._fwd_logits[h.nb][:h.n].float().clone())
         st.h_out[:h.n].copy_(self.d_out[:h.n], non_blocking=True)
         st.err_armed = False
         st.event.record()
@@ -1156,7 +1277,8 @@ class ModelRunner:
             self.stats["deferred_mixed"] = self.stats.get("deferred_mixed", 0) + 1
         else:
             dmask = dev[len(names) + 7] if masks is not None else None
-            self._mixed_sample(mh, logits, samp, dmask, dev[-4:] if pen is not None else None)
+            self._mixed_sample(mh, logits, samp, dmask, dev[-4:] if pen is not None else None,
+                               host["lp"])
         if self._gaps is not None:
             self._gap_mark(False)
         tp4 = time.perf_counter()
@@ -1169,8 +1291,11 @@ class ModelRunner:
         ml["n"] += 1
         return mh
 
-    def _mixed_sample(self, mh: "MixedHandle", logits, samp, dmask, pen=None):
+    def _mixed_sample(self, mh: "MixedHandle", logits, samp, dmask, pen=None, lp_want=None):
         self._pen_sample(logits, samp, dmask, pen, out=self.d_out[:mh.n])
+        mh.lp.n = 0
+        if lp_want is not None:
+            self._lp_launch(mh.lp, lp_want, logits, self.d_out)
         mh.host[:mh.n].copy_(self.d_out[:mh.n], non_blocking=self.is_gpu)
         if mh.event is not None:
             mh.event.record()
@@ -1314,6 +1439,8 @@ class ModelRunner:
             g = self._capture(nb, pen)
         g.replay()
         self.stats["graph_replays"] += 1
+        if st.lp_want is not None:   # on the graph's raw logits, before the next replay overwrites them
+            self._lp_launch(st.lp, st.lp_want, self._graph_logits[(nb, pen)], self.d_out)
         st.h_out[:n].copy_(self.d_out[:n], non_blocking=True)
         flag = self.comm.error_flag if self.checks_comm else None
         st.err_armed = flag is not None

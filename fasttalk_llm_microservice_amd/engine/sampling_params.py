@@ -24,6 +24,28 @@ def pick_penalties(src) -> dict:
     return out
 
 
+LOGPROBS_MAX = 20   # OpenAI's cap on top_logprobs (ops.LOGPROBS_MAX)
+
+
+def pick_logprobs(src) -> Optional[int]:
+    """OpenAI's pair ``logprobs: true`` / ``top_logprobs: n`` of a request body as
+    SamplingParams.logprobs: None when the request does not ask, else n (0 without
+    ``top_logprobs``).  ``top_logprobs`` without ``logprobs: true``, a non-integer or an
+    n outside 0..20 raises ValueError."""
+    on, top = src.get("logprobs"), src.get("top_logprobs")
+    if on is not None and not isinstance(on, bool):
+        raise ValueError("logprobs must be true or false")
+    if top is None:
+        return 0 if on else None
+    if isinstance(top, bool) or not isinstance(top, int):
+        raise ValueError("top_logprobs must be an integer")
+    if not on:
+        raise ValueError("top_logprobs requires logprobs: true")
+    if not 0 <= top <= LOGPROBS_MAX:
+        raise ValueError(f"top_logprobs must be in 0..{LOGPROBS_MAX}")
+    return top
+
+
 @dataclasses.dataclass
 class SamplingParams:
     temperature: float = 0.7
@@ -53,8 +75,19 @@ class SamplingParams:
     frequency_penalty: float = 0.0
     # OpenAI: token id (int or decimal str, as in the JSON) -> bias in [-100, 100]
     logit_bias: Optional[dict] = None
+    # per-token logprobs over the RAW logits (before the processors above, the
+    # allow-mask, temperature, top-k and top-p; vLLM's default): None = off, 0..20 = the
+    # sampled token's logprob plus that many most likely alternatives
+    logprobs: Optional[int] = None
 
     MAX_LOGIT_BIAS = 300
+
+    def _check_logprobs(self):
+        v = self.logprobs
+        if v is None:
+            return
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= LOGPROBS_MAX:
+            raise ValueError(f"logprobs must be None or an integer in 0..{LOGPROBS_MAX}")
 
     @property
     def has_penalties(self) -> bool:
@@ -97,6 +130,7 @@ class SamplingParams:
 
     def __post_init__(self):
         self._check_penalties()
+        self._check_logprobs()
         if self.temperature is None:
             self.temperature = 0.7
         if self.temperature < 0:

@@ -31,6 +31,9 @@ class RequestOutput:
     num_output_tokens: int = 0
     ttft_s: Optional[float] = None
     error: Optional[str] = None
+    # SamplingParams.logprobs: one (token_id, logprob, [(alt_id, alt_logprob), ...]) per
+    # entry of token_ids; None when the request did not ask
+    logprobs: Optional[list] = None
 
 
 class Sequence:
@@ -129,12 +132,15 @@ def coalesce(first: RequestOutput, q) -> RequestOutput:
         return first
     text = [first.text]
     ids = list(first.token_ids)
+    lps = None if first.logprobs is None else list(first.logprobs)
     o = first
     while not q.empty() and not o.finished:
         o = q.get_nowait()
         text.append(o.text)
         ids.extend(o.token_ids)
-    return RequestOutput(first.request_id, "".join(text), ids, finished=o.finished,
+        if lps is not None and o.logprobs is not None:
+            lps.extend(o.logprobs)
+    return RequestOutput(first.request_id, "".join(text), ids, finished=o.finished, logprobs=lps,
                          finish_reason=o.finish_reason,
                          num_prompt_tokens=first.num_prompt_tokens or o.num_prompt_tokens,
                          num_cached_tokens=first.num_cached_tokens or o.num_cached_tokens,

@@ -444,6 +444,31 @@ def penalty_apply(logits, slots, rep, pres, freq, table, bias_ids, bias_vals, ou
     return out
 
 
+# ---------------------------------------------------------------------------------
+# per-token logprobs (csrc/kernels/logprobs.hip)
+# ---------------------------------------------------------------------------------
+
+LOGPROBS_MAX = ref.LOGPROBS_MAX   # alternatives per token (OpenAI's cap on top_logprobs)
+
+
+def logprobs(logits, sampled, want, out_lp=None, out_id=None):
+    """``(out_lp fp32, out_id int32)`` [B, 1 + LOGPROBS_MAX] of a step's RAW ``logits``
+    [B, V] (bf16 / fp32; on the GPU rows 16-B aligned, V any): per row with ``want[r]``
+    in 0..LOGPROBS_MAX, column 0 = the sampled id ``sampled[r]`` and its logprob, columns
+    1..want[r] = the most likely tokens (logit descending, ties to the lower id), the
+    rest id -1 / logprob 0.0; rows with ``want[r] == -1`` are left untouched
+    (reference.token_logprobs)."""
+    if not logits.is_cuda:
+        return ref.token_logprobs(logits, sampled, want, out_lp, out_id)
+    b = logits.shape[0]
+    if out_lp is None:
+        out_lp = torch.zeros(b, 1 + LOGPROBS_MAX, dtype=torch.float32, device=logits.device)
+    if out_id is None:
+        out_id = torch.full((b, 1 + LOGPROBS_MAX), -1, dtype=torch.int32, device=logits.device)
+    native().logprobs(logits, sampled, want, out_lp, out_id)
+    return out_lp, out_id
+
+
 def kv_block_copy(k_cache, v_cache, pairs: torch.Tensor):
     if k_cache.is_cuda:
         native().kv_block_copy(k_cache, v_cache, pairs)

@@ -216,6 +216,54 @@ def apply_penalties(logits: torch.Tensor, prompt_mask: torch.Tensor, counts: tor
     return torch.where(touched, y.to(logits.dtype), logits)
 
 
+LOGPROBS_MAX = 20   # OpenAI's cap on top_logprobs (csrc/kernels/logprobs.hip kLpMax)
+
+
+def token_logprobs(logits: torch.Tensor, sampled, want, out_lp: Optional[torch.Tensor] = None,
+                   out_id: Optional[torch.Tensor] = None):
+    """Per-token logprobs of a step (SamplingParams.logprobs), the reference of
+    csrc/kernels/logprobs.hip: ``(out_lp fp32, out_id int32)``, both [B, 1 + 20].
+
+    ``logits`` [B, V] are the RAW logits (before penalties, bias, mask, temperature,
+    top-k / top-p), widened to fp32; ``logprob = log_softmax(x)``.  Per row with
+    ``want[r] >= 0``: column 0 holds the sampled id and its logprob, columns
+    1..want[r] the want[r] most likely tokens (logit descending, ties to the lower
+    id), the rest id -1 / logprob 0.0.  Rows with ``want[r] == -1`` asked for nothing:
+    their output rows are left as they are (new outputs: id -1, logprob 0.0)."""
+    x = logits.float()
+    b, _ = x.shape
+    cols = 1 + LOGPROBS_MAX
+    if out_lp is None:
+        out_lp = torch.zeros(b, cols, dtype=torch.float32, device=x.device)
+    if out_id is None:
+        out_id = torch.full((b, cols), -1, dtype=torch.int32, device=x.device)
+    want = torch.as_tensor(want, dtype=torch.int64, device=x.device).reshape(-1)[:b]
+    sampled = torch.as_tensor(sampled, dtype=torch.int64, device=x.device).reshape(-1)[:b]
+    rows = torch.nonzero(want >= 0).flatten()
+    if not rows.numel():
+        return out_lp, out_id
+    if int(want.max()) > LOGPROBS_MAX:
+        raise ValueError(f"token_logprobs: more than {LOGPROBS_MAX} alternatives asked")
+    xr = x[rows]
+    lp = torch.log_softmax(xr, dim=-1)
+    # a -inf logit has logprob -inf also in a row that is -inf throughout (never NaN)
+    lp = torch.where(xr == float("-inf"), xr, lp)
+    # +0.0 so that -0.0 and 0.0 tie (the id decides), as they compare equal
+    order = torch.sort(xr + 0.0, dim=-1, descending=True, stable=True).indices[:, :LOGPROBS_MAX]
+    k = order.shape[1]
+    s = sampled[rows]
+    res_lp = torch.zeros(rows.numel(), cols, dtype=torch.float32, device=x.device)
+    res_id = torch.full((rows.numel(), cols), -1, dtype=torch.int32, device=x.device)
+    res_lp[:, 0] = lp.gather(1, s.view(-1, 1)).flatten()
+    res_id[:, 0] = s.to(torch.int32)
+    keep = torch.arange(k, device=x.device).view(1, -1) < want[rows].view(-1, 1)
+    res_lp[:, 1:1 + k] = torch.where(keep, lp.gather(1, order), torch.zeros(()))
+    res_id[:, 1:1 + k] = torch.where(keep, order.to(torch.int32), torch.full((), -1, dtype=torch.int32))
+    out_lp[rows] = res_lp
+    out_id[rows] = res_id
+    return out_lp, out_id
+
+
 def sample(logits: torch.Tensor, temperature, top_p, top_k, seeds, steps,
            mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Reference sampler (CPU backend).  Same contract as the HIP kernel:
