@@ -137,10 +137,11 @@ class NativeHandler:
         self.max_model_len = inner.max_model_len
         self.model = model or getattr(inner.model_cfg, "name", "native")
         self.default_max_tokens = default_max_tokens
-        # DEFAULT_REPETITION_PENALTY / _PRESENCE_ / _FREQUENCY_: what a request leaves out
+        # DEFAULT_REPETITION_PENALTY / _PRESENCE_ / _FREQUENCY_ / DEFAULT_MIN_P: what a
+        # request leaves out
         self.default_penalties: Dict[str, Any] = {
             k: float(getattr(config, "default_" + k))
-            for k in ("repetition_penalty", "presence_penalty", "frequency_penalty")
+            for k in ("repetition_penalty", "presence_penalty", "frequency_penalty", "min_p")
             if getattr(config, "default_" + k, None) is not None}
         self._active: Dict[str, str] = {}      # session/request key -> engine request id
         self._sessions: Dict[str, _SessionTokens] = {}
@@ -330,8 +331,9 @@ class NativeHandler:
                 guided=None, ignore_eos=False, min_tokens=0, guided_lazy=False, priority=0,
                 penalties=None, logprobs=None):
         """``penalties``: repetition_penalty / presence_penalty / frequency_penalty /
-        logit_bias (engine.sampling_params.pick_penalties); the service defaults
-        (DEFAULT_REPETITION_PENALTY ...) fill in what a request leaves out.
+        logit_bias (engine.sampling_params.pick_penalties), and ``min_p`` (pick_min_p),
+        which travels with them; the service defaults (DEFAULT_REPETITION_PENALTY ...,
+        DEFAULT_MIN_P) fill in what a request leaves out.
         ``logprobs``: SamplingParams.logprobs (pick_logprobs), None = off."""
         from fasttalk_llm_microservice_amd.engine.sampling_params import SamplingParams
 

@@ -60,12 +60,13 @@ class OllamaHandler:
         req_id = request_id or f"ollama-{uuid.uuid4()}"
         options = {k: v for k, v in (("temperature", temperature), ("num_predict", max_tokens),
                                      ("top_p", top_p), ("top_k", top_k), ("stop", stop)) if v is not None}
-        # Ollama's options know repeat_penalty / presence_penalty / frequency_penalty (no
-        # logit_bias); values at their neutral defaults are left out
+        # Ollama's options know repeat_penalty / presence_penalty / frequency_penalty / min_p
+        # (no logit_bias); values at their neutral defaults are left out
         pen = penalties or {}
         for name, key, neutral in (("repeat_penalty", "repetition_penalty", 1.0),
                                    ("presence_penalty", "presence_penalty", 0.0),
-                                   ("frequency_penalty", "frequency_penalty", 0.0)):
+                                   ("frequency_penalty", "frequency_penalty", 0.0),
+                                   ("min_p", "min_p", 0.0)):
             if pen.get(key) is not None and float(pen[key]) != neutral:
                 options[name] = float(pen[key])
         payload = {"model": self.model, "messages": messages, "stream": True, "options": options,

@@ -58,7 +58,9 @@ def register_openai_routes(app, handler) -> None:
                   seed=body.get("seed"), ignore_eos=bool(body.get("ignore_eos", False)),
                   min_tokens=int(body.get("min_tokens") or 0))
         # presence_penalty / frequency_penalty / logit_bias, and vLLM's repetition_penalty
+        # and min_p (it travels with the penalties)
         from fasttalk_llm_microservice_amd.engine.sampling_params import (pick_logprobs,
+                                                                           pick_min_p,
                                                                            pick_penalties)
 
         def bad_request(msg: str):
@@ -66,10 +68,16 @@ def register_openai_routes(app, handler) -> None:
                                 status_code=400)
 
         try:
-            kw["penalties"] = pick_penalties(body) or None
+            pen = pick_penalties(body)
+            pen.update(pick_min_p(body))
+            kw["penalties"] = pen or None
             want_lp = pick_logprobs(body)
         except (ValueError, TypeError) as e:
             return bad_request(str(e))
+        if pen.get("min_p"):
+            inner = getattr(handler.engine, "engine", handler.engine)
+            if int(getattr(getattr(inner, "cfg", None), "tp_size", 1) or 1) > 1:
+                return bad_request("min_p is not supported with tensor parallelism yet")
         if want_lp is not None:
             # logprobs / top_logprobs: per-token logprobs over the raw logits.  Not with a
             # grammar (forced tokens have no sampled logit) nor tool parsing, nor under TP.

@@ -24,12 +24,12 @@ logger = logging.getLogger(__name__)
 
 def remote_penalties(penalties: Optional[Dict[str, Any]]) -> Dict[str, Any]:
     """OpenAI / vLLM request-body fields of the sampler penalties a session set:
-    presence_penalty, frequency_penalty, logit_bias and vLLM's repetition_penalty;
-    values at their neutral defaults are left out."""
+    presence_penalty, frequency_penalty, logit_bias and vLLM's repetition_penalty and
+    min_p (which travels with them); values at their neutral defaults are left out."""
     pen = penalties or {}
     out: Dict[str, Any] = {}
     for key, neutral in (("repetition_penalty", 1.0), ("presence_penalty", 0.0),
-                         ("frequency_penalty", 0.0)):
+                         ("frequency_penalty", 0.0), ("min_p", 0.0)):
         if pen.get(key) is not None and float(pen[key]) != neutral:
             out[key] = float(pen[key])
     if pen.get("logit_bias"):

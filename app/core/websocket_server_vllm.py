@@ -41,20 +41,22 @@ logger = get_logger(__name__)
 
 GEN_KEYS = ("temperature", "max_tokens", "top_p", "top_k", "stop", "seed", "min_tokens",
             "ignore_eos", "repetition_penalty", "presence_penalty", "frequency_penalty",
-            "logit_bias")
+            "logit_bias", "min_p")
 GEN_ALIASES = {"repeat_penalty": "repetition_penalty"}   # Ollama's name
 
 
 def gen_config(cfg: Dict[str, Any]) -> Dict[str, Any]:
     """The generation keys of a ``start_session`` / ``update_config`` config, aliases
-    resolved and the penalty fields validated (ValueError -> the ``error`` frame)."""
-    from fasttalk_llm_microservice_amd.engine.sampling_params import pick_penalties
+    resolved and the penalty fields and ``min_p`` validated (ValueError -> the ``error``
+    frame)."""
+    from fasttalk_llm_microservice_amd.engine.sampling_params import pick_min_p, pick_penalties
 
     out = {k: cfg[k] for k in GEN_KEYS if k in cfg}
     for alias, k in GEN_ALIASES.items():
         if alias in cfg and k not in out:
             out[k] = cfg[alias]
     pick_penalties(out)
+    pick_min_p(out)
     return out
 AGENT_KEYS = ("enable_web_search", "enable_tools", "system_prompt", "vllm_model", "vllm_base_url")
 
@@ -407,7 +409,9 @@ class WebSocketLLMServer:
             "repetition_penalty": sc.get("repetition_penalty", c.default_repetition_penalty),
             "presence_penalty": sc.get("presence_penalty", c.default_presence_penalty),
             "frequency_penalty": sc.get("frequency_penalty", c.default_frequency_penalty),
-            "logit_bias": sc.get("logit_bias")}
+            "logit_bias": sc.get("logit_bias"),
+            # min_p travels with them (DEFAULT_MIN_P; 0 = off)
+            "min_p": sc.get("min_p", c.default_min_p)}
         return out
 
     async def _handle_user_message(self, session_id: str, message: Dict[str, Any], send):

@@ -99,6 +99,8 @@ class Config:
         default_factory=lambda: float(_e("DEFAULT_REPETITION_PENALTY", "1.0")))
     default_presence_penalty: float = field(
         default_factory=lambda: float(_e("DEFAULT_PRESENCE_PENALTY", "0.0")))
+    # min_p a session does not set itself (0 = off)
+    default_min_p: float = field(default_factory=lambda: float(_e("DEFAULT_MIN_P", "0.0")))
     default_frequency_penalty: float = field(
         default_factory=lambda: float(_e("DEFAULT_FREQUENCY_PENALTY", "0.0")))
     # ---- server
@@ -154,6 +156,8 @@ class Config:
              f"repetition_penalty must be > 0, got {self.default_repetition_penalty}"),
             (-2.0 <= self.default_presence_penalty <= 2.0,
              f"presence_penalty must be between -2.0 and 2.0, got {self.default_presence_penalty}"),
+            (0.0 <= self.default_min_p <= 1.0,
+             f"min_p must be between 0.0 and 1.0, got {self.default_min_p}"),
             (-2.0 <= self.default_frequency_penalty <= 2.0,
              f"frequency_penalty must be between -2.0 and 2.0, got {self.default_frequency_penalty}"),
             (1024 <= self.port <= 65535, f"Port must be between 1024 and 65535, got {self.port}"),
@@ -208,7 +212,7 @@ class Config:
                 "monitoring_port", "max_connections", "default_temperature", "default_max_tokens",
                 "default_context_window", "default_top_p", "default_top_k",
                 "default_repetition_penalty", "default_presence_penalty",
-                "default_frequency_penalty", "num_threads",
+                "default_frequency_penalty", "default_min_p", "num_threads",
                 "num_workers", "log_level"]
         d: Dict[str, Any] = {k: getattr(self, k) for k in keys}
         if self.llm_provider in ("vllm", "openai"):

@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--frequency-penalty", type=float, default=0.0)
     # per-token logprobs with N alternatives on every row (ops.logprobs behind every sampler)
     ap.add_argument("--logprobs", type=int, default=None)
+    # min_p on every row (the decode graph's sampler then reads the ln(min_p) array)
+    ap.add_argument("--min-p", type=float, default=0.0)
     a = ap.parse_args()
 
     import numpy as np
@@ -51,7 +53,8 @@ def main():
         prompts = [rng.integers(0, 120000, a.prompt).tolist() for _ in range(a.seqs)]
         sp = SamplingParams(temperature=a.temperature, top_p=0.9, max_tokens=a.gen, ignore_eos=True,
                             repetition_penalty=a.repetition_penalty,
-                            frequency_penalty=a.frequency_penalty, logprobs=a.logprobs)
+                            frequency_penalty=a.frequency_penalty, logprobs=a.logprobs,
+                            min_p=a.min_p)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i, p in enumerate(prompts):
@@ -69,7 +72,8 @@ def main():
         res.append({"round": r, "tokens": ntok, "seconds": dt, "tok_s": ntok / dt,
                     "ttft_s": first, "decode_step_ms": m["decode_step_ms_avg"],
                     "prefill_step_ms": m["prefill_step_ms_avg"],
-                    "penalty_steps": m["penalty_steps"], "logprob_steps": m["logprob_steps"]})
+                    "penalty_steps": m["penalty_steps"], "logprob_steps": m["logprob_steps"],
+                    "min_p_steps": m["min_p_steps"]})
         print(json.dumps(res[-1]), flush=True)
     print(json.dumps({"final": res[-1], "runner": eng.runner.stats}), flush=True)
 

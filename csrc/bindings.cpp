@@ -39,7 +39,8 @@ int ft_prefill_attention(void* out, int out_stride, const void* q, int q_stride,
 int ft_sample(int* out_tokens, const void* logits, int logits_is_bf16, long logit_stride,
               int batch, int vocab, const float* temperature, const float* top_p,
               const int* top_k, const long long* seeds, const int* steps,
-              const uint32_t* allow_mask, int mask_words, float* ws, hipStream_t stream);
+              const uint32_t* allow_mask, int mask_words, float* ws, const float* ln_min_p,
+              hipStream_t stream);
 int ft_sample_ws_floats();
 int ft_logprobs_max();
 int ft_logprobs_ws_words();
@@ -356,7 +357,8 @@ void prefill_attention(at::Tensor out, at::Tensor q, at::Tensor k_cache, at::Ten
 }
 
 void sample(at::Tensor out_tokens, at::Tensor logits, at::Tensor temperature, at::Tensor top_p,
-            at::Tensor top_k, at::Tensor seeds, at::Tensor steps, c10::optional<at::Tensor> mask) {
+            at::Tensor top_k, at::Tensor seeds, at::Tensor steps, c10::optional<at::Tensor> mask,
+            c10::optional<at::Tensor> ln_min_p) {
   check_i32(out_tokens, "out_tokens");
   check_dev(logits, "logits");
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits [B, V] with contiguous rows");
@@ -380,6 +382,15 @@ void sample(at::Tensor out_tokens, at::Tensor logits, at::Tensor temperature, at
     TORCH_CHECK(mask->size(0) >= batch && words * 32 >= vocab, "mask shape");
     mp = reinterpret_cast<const uint32_t*>(mask->data_ptr<int>());
   }
+  // ln(min_p) per row, -inf = off; absent: the sampler's launches without min_p
+  const float* lmp = nullptr;
+  if (ln_min_p.has_value() && ln_min_p->defined()) {
+    check_dev(*ln_min_p, "ln_min_p");
+    TORCH_CHECK(ln_min_p->scalar_type() == at::kFloat && ln_min_p->is_contiguous() &&
+                    ln_min_p->numel() >= batch,
+                "ln_min_p fp32, contiguous, one per row");
+    lmp = ln_min_p->data_ptr<float>();
+  }
   // per-row scratch of the multi-workgroup sampler (stream-ordered: safe to reuse
   // from the caching allocator, graph-capturable); FT_SAMPLER_ONE_WG=1 keeps the
   // single-workgroup kernel for every row
@@ -394,7 +405,7 @@ void sample(at::Tensor out_tokens, at::Tensor logits, at::Tensor temperature, at
                      top_p.data_ptr<float>(), top_k.data_ptr<int>(),
                      reinterpret_cast<const long long*>(seeds.data_ptr<int64_t>()),
                      steps.data_ptr<int>(), mp, words, one_wg ? nullptr : ws.data_ptr<float>(),
-                     cur_stream()),
+                     lmp, cur_stream()),
            "sample");
 }
 
@@ -1143,7 +1154,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("prefill_tile_tokens", [](int64_t nq, int64_t nkv) { return ft_prefill_tile_tokens((int)nq, (int)nkv); });
   m.def("sample", &sample, py::arg("out_tokens"), py::arg("logits"), py::arg("temperature"),
         py::arg("top_p"), py::arg("top_k"), py::arg("seeds"), py::arg("steps"),
-        py::arg("mask") = py::none());
+        py::arg("mask") = py::none(), py::arg("ln_min_p") = py::none());
   m.def("penalty_apply", &penalty_apply);
   m.def("penalty_update", &penalty_update);
   m.def("penalty_seed", &penalty_seed);

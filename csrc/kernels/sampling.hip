@@ -47,6 +47,26 @@ __device__ __forceinline__ float key_to_f32(uint32_t k) {
   return __uint_as_float(b << 16);
 }
 
+// min_p: ordered key of the smallest bf16 value >= M + temp * lnmp (lnmp = ln(min_p),
+// finite, <= 0; M = the row's maximal allowed bf16-rounded logit).  A token is kept
+// iff key >= this key, i.e. iff float(bf16(x)) >= M + temp * lnmp with the product
+// and the sum each rounded to fp32 (no FMA), as ops/reference.py sample evaluates
+// it.  Never below kNegInfKey + 1, so masked ids stay out; never above key(M), so
+// the argmax is always kept.
+__device__ __forceinline__ uint32_t minp_key(float M, float temp, float lnmp) {
+  float t;
+  {
+#pragma clang fp contract(off)
+    const float prod = temp * lnmp;
+    t = M + prod;
+  }
+  uint32_t u = __float_as_uint(t);
+  if (t == 0.f) u = 0x80000000u;   // -0.0 >= +0.0: both zeros are kept
+  // round towards +inf to bf16: magnitude up for t > 0, truncated for t < 0
+  const uint32_t b = (u & 0x80000000u) ? (u >> 16) : ((u + 0xFFFFu) >> 16);
+  return max(bf16_to_key(b), kNegInfKey + 1u);
+}
+
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -188,13 +208,15 @@ constexpr int kWsStats = 0, kWsMZ = 4 * kSlices, kWsCand = kWsMZ + 2, kWsAbove =
               kWsFlag = kWsAbove + kCand * kSlices, kWsTkCnt = kWsFlag + 1,
               kWsTk = kWsTkCnt + kSlices, kWsRow = kWsTk + 2 * kSlices * kTopkMax;
 
-template <typename T>
-__global__ __launch_bounds__(kSampThreads) void sample_kernel(
+// MP: the row's ln(min_p) is read from ln_min_p (-inf = off); without MP the pointer is
+// not touched and every min_p branch is compiled out (if constexpr)
+template <typename T, bool MP>
+__device__ __forceinline__ void sample_body(
     int* __restrict__ out_tokens, const T* __restrict__ logits, long logit_stride, int vocab,
     const float* __restrict__ temperature, const float* __restrict__ top_p,
     const int* __restrict__ top_k, const long long* __restrict__ seeds,
     const int* __restrict__ steps, const uint32_t* __restrict__ allow_mask, int mask_words,
-    const int* __restrict__ flags, int flag_stride) {
+    const int* __restrict__ flags, int flag_stride, const float* __restrict__ ln_min_p) {
   __shared__ SampShared sh;
   __shared__ float chunk_mass[kChunks * kSampThreads];  // 64 KiB
   const int row = blockIdx.x;
@@ -304,6 +326,17 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(
       lo = (c3 >= k) ? t3 : (c2 >= k) ? t2 : (c1 >= k) ? t1 : lo;
     }
     if (lo > thr) thr = lo;
+  }
+  // ---- min_p: top-k and min_p together keep key >= the higher of the two thresholds.  Recomputed here from
+  // this kernel's own M also for a fallback row (fl == 1); everything below tests
+  // key >= thr, so the masses, the draw, the rejection rounds and the nucleus search
+  // inherit it
+  if constexpr (MP) {
+    const float lnmp = ln_min_p[row];
+    if (lnmp > -INFINITY) {
+      const uint32_t tk = minp_key(M, temp, lnmp);
+      if (tk > thr) thr = tk;
+    }
   }
 
   // ---- per-chunk masses of kept tokens (LDS), per-thread totals -------------------------
@@ -461,6 +494,28 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(
   if (tid == 0) out_tokens[row] = FT_CHECK_IDX(chosen, vocab, kCkSampled, row);
 }
 
+#define FT_SAMPLE_ARGS                                                                          \
+  int *__restrict__ out_tokens, const T *__restrict__ logits, long logit_stride, int vocab,      \
+      const float *__restrict__ temperature, const float *__restrict__ top_p,                    \
+      const int *__restrict__ top_k, const long long *__restrict__ seeds,                        \
+      const int *__restrict__ steps, const uint32_t *__restrict__ allow_mask, int mask_words
+#define FT_SAMPLE_PASS                                                                          \
+  out_tokens, logits, logit_stride, vocab, temperature, top_p, top_k, seeds, steps, allow_mask, \
+      mask_words
+
+template <typename T>
+__global__ __launch_bounds__(kSampThreads) void sample_kernel(
+    FT_SAMPLE_ARGS, const int* __restrict__ flags, int flag_stride) {
+  sample_body<T, false>(FT_SAMPLE_PASS, flags, flag_stride, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSampThreads) void sample_minp_kernel(
+    FT_SAMPLE_ARGS, const int* __restrict__ flags, int flag_stride,
+    const float* __restrict__ ln_min_p) {
+  sample_body<T, true>(FT_SAMPLE_PASS, flags, flag_stride, ln_min_p);
+}
+
 // ---------------------------------------------------------------------------
 // Multi-workgroup path for the rows without top-k (the serving default: greedy,
 // or temperature + top-p).  One 1024-thread workgroup per row is VALU bound on a
@@ -468,6 +523,8 @@ __global__ __launch_bounds__(kSampThreads) void sample_kernel(
 // the vocabulary is cut into kSlices slices, each streamed by its own workgroup:
 //   K1 slice stats     (rows x kSlices): argmax key / id, and the slice's mass
 //                      Z_p = sum exp2((x - M_p) c) relative to its own max M_p
+//   K1b min_p          (rows x kSlices, launched only when a ln(min_p) array is given):
+//                      a min_p row's Z_p becomes the mass of its kept ids only
 //   K2 draw            (rows): M, Z = sum Z_p 2^((M_p - M) c); greedy rows end
 //                      here; kCand inverse-CDF candidates (uniforms u0..u3 of the
 //                      same splitmix64 stream): slice by the prefix of the Z_p,
@@ -710,19 +767,62 @@ __global__ __launch_bounds__(kSlThreads) void samp_stats_kernel(
   }
 }
 
+// min_p rows without top-k: the kept set depends on the row's global max M, which the
+// slices only know once samp_stats_kernel has ended, so this second launch (the launch
+// boundary is the synchronisation: no workgroup waits on another) re-sums slice p over
+// its kept ids, key >= minp_key(M, ..), still relative to the slice's own max M_p, and
+// overwrites Z_p.  The draw kernel's Z_p * 2^((M_p - M) c) is then the slice's kept
+// mass.  Only Z_p is written and only the M_q are read, so the workgroups of a row do
+// not race; a slice whose max is below the threshold gets Z_p = 0 and is never drawn.
+// Indexes exactly what samp_stats_kernel indexes.  Rows without min_p, top-k rows and
+// greedy rows return at once.
 template <typename T>
-__global__ __launch_bounds__(kSampThreads) void samp_draw_kernel(
+__global__ __launch_bounds__(kSlThreads) void samp_minp_kernel(
+    const T* __restrict__ logits, long stride, int vocab, const float* __restrict__ temperature,
+    const int* __restrict__ top_k, const uint32_t* __restrict__ allow_mask, int mask_words,
+    const float* __restrict__ ln_min_p, float* __restrict__ ws) {
+  __shared__ float sf[kSlThreads / 64];
+  const int row = blockIdx.y, p = blockIdx.x;
+  const float lnmp = ln_min_p[row];
+  const float temp = temperature[row];
+  if (!(lnmp > -INFINITY) || !(temp > 0.f) || topk_row(top_k, row, vocab)) return;
+  float* st = ws + (long)row * kWsRow + kWsStats;
+  const float Mp = st[4 * p];
+  if (Mp == -INFINITY) return;   // nothing allowed in this slice: Z_p is 0 already
+  float M = Mp;
+#pragma unroll
+  for (int q = 0; q < kSlices; ++q) M = fmaxf(M, st[4 * q]);
+  const uint32_t tk = minp_key(M, temp, lnmp);
+  const T* x = logits + (long)row * stride;
+  const uint32_t* mrow = allow_mask ? allow_mask + (long)row * mask_words : nullptr;
+  const int S = slice_len(vocab);
+  const int beg = p * S, end = min(vocab, beg + S);
+  const float cexp = 1.4426950408889634f / temp;
+  float z = 0.f;
+  for (int base = beg + threadIdx.x * 8; base < end; base += kSlThreads * 8) {
+    uint32_t key[8];
+    load_keys8<T>(x, mrow, base, vocab, key);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z += key[j] >= tk ? exp2f((key_to_f32(key[j]) - Mp) * cexp) : 0.f;
+  }
+  z = wg_sum(z, sf);
+  if (threadIdx.x == 0) st[4 * p + 1] = z;
+}
+
+template <typename T, bool MP>
+__device__ __forceinline__ void samp_draw_body(
     int* __restrict__ out_tokens, const T* __restrict__ logits, long stride, int vocab,
     const float* __restrict__ temperature, const float* __restrict__ top_p,
     const int* __restrict__ top_k, const long long* __restrict__ seeds,
     const int* __restrict__ steps, const uint32_t* __restrict__ allow_mask, int mask_words,
-    float* __restrict__ ws) {
+    float* __restrict__ ws, const float* __restrict__ ln_min_p) {
   static_assert(kSlices <= 64, "one lane per slice");
   // top-p rows: candidate r is searched by threads [r * per, (r + 1) * per), per = kSampThreads /
   // kCand; without a nucleus only candidate 0 is drawn, by the whole workgroup
   __shared__ float s_scan[kSampThreads / 64];
   __shared__ float s_M, s_cexp, s_tgt[kCand];
   __shared__ int s_ps[kCand], s_done, s_last[kCand], s_found[kCand];
+  __shared__ uint32_t s_tk;   // min_p rows: ids with key < s_tk are dropped
   const int row = blockIdx.x, tid = threadIdx.x, lane = lane_id();
   float* wr = ws + (long)row * kWsRow;
   int* flag = reinterpret_cast<int*>(wr + kWsFlag);
@@ -799,6 +899,12 @@ __global__ __launch_bounds__(kSampThreads) void samp_draw_kernel(
           s_tgt[r] = tgt;
         }
       }
+      if constexpr (MP) {
+        // the same M and threshold as samp_minp_kernel, whose kept masses the Z_p now
+        // are: Z is the kept mass Z_kept, which the accept step compares against
+        const float lnmp = ln_min_p[row];
+        if (lane == 0) s_tk = lnmp > -INFINITY ? minp_key(M, temp, lnmp) : kNegInfKey + 1u;
+      }
       if (lane == 0) {
         s_M = M;
         s_cexp = cexp;
@@ -825,6 +931,11 @@ __global__ __launch_bounds__(kSampThreads) void samp_draw_kernel(
   const int r = tid / per, lt = tid - r * per, w = lt >> 6;
   float* scan = s_scan + r * (per >> 6);
   const float M = s_M, cexp = s_cexp, tgt = s_tgt[r];
+  // kept ids: allowed and, on a min_p row, not below the threshold.  The in-slice
+  // masses, the walk and both rounding tails (s_last: the last thread with kept mass;
+  // lastk: a thread's last kept id) test it, so a tail never picks a dropped id
+  uint32_t tk = kNegInfKey + 1u;
+  if constexpr (MP) tk = s_tk;
   const int S = slice_len(vocab);
   const int beg = s_ps[r] * S, end = min(vocab, beg + S);
   const uint32_t* mrow = allow_mask ? allow_mask + (long)row * mask_words : nullptr;
@@ -834,12 +945,12 @@ __global__ __launch_bounds__(kSampThreads) void samp_draw_kernel(
   {
     load_keys8<T>(x, mrow, beg + lt * 8 < end ? beg + lt * 8 : vocab, vocab, k0);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) mass += k0[j] > kNegInfKey ? exp2f((key_to_f32(k0[j]) - M) * cexp) : 0.f;
+    for (int j = 0; j < 8; ++j) mass += k0[j] >= tk ? exp2f((key_to_f32(k0[j]) - M) * cexp) : 0.f;
     for (int b2 = beg + (lt + per) * 8; b2 < end; b2 += per * 8) {
       uint32_t key[8];
       load_keys8<T>(x, mrow, b2, vocab, key);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) mass += key[j] > kNegInfKey ? exp2f((key_to_f32(key[j]) - M) * cexp) : 0.f;
+      for (int j = 0; j < 8; ++j) mass += key[j] >= tk ? exp2f((key_to_f32(key[j]) - M) * cexp) : 0.f;
     }
   }
   float incl = mass;
@@ -863,7 +974,7 @@ __global__ __launch_bounds__(kSampThreads) void samp_draw_kernel(
     auto walk = [&](const uint32_t (&key)[8], int base) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        if (pick < 0 && key[j] > kNegInfKey) {
+        if (pick < 0 && key[j] >= tk) {
           const float pj = exp2f((key_to_f32(key[j]) - M) * cexp);
           lastk = base + j;
           lastkey = key[j];
@@ -900,6 +1011,22 @@ __global__ __launch_bounds__(kSampThreads) void samp_draw_kernel(
     }
   }
 }
+
+template <typename T>
+__global__ __launch_bounds__(kSampThreads) void samp_draw_kernel(FT_SAMPLE_ARGS,
+                                                                 float* __restrict__ ws) {
+  samp_draw_body<T, false>(FT_SAMPLE_PASS, ws, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSampThreads) void samp_draw_minp_kernel(
+    FT_SAMPLE_ARGS, float* __restrict__ ws, const float* __restrict__ ln_min_p) {
+  samp_draw_body<T, true>(FT_SAMPLE_PASS, ws, ln_min_p);
+}
+
+// min_p needs no change here: a candidate is a kept id (or the argmax), and every id
+// strictly more likely than a kept id is itself kept, so the above-mass over all
+// allowed ids is the above-mass over the kept set.
 
 template <typename T>
 __global__ __launch_bounds__(kSlThreads) void samp_above_kernel(
@@ -947,10 +1074,12 @@ __global__ __launch_bounds__(kSlThreads) void samp_above_kernel(
 // rank-ordered prefix sum -- deterministic whatever order the candidates were
 // appended in.  Rows whose
 // candidates or kept set overflow go to the one-workgroup kernel (flag 2).
-__global__ __launch_bounds__(kSlThreads) void samp_topk_kernel(
+template <bool MP>
+__device__ __forceinline__ void samp_topk_body(
     int* __restrict__ out_tokens, int vocab, const float* __restrict__ temperature,
     const float* __restrict__ top_p, const int* __restrict__ top_k,
-    const long long* __restrict__ seeds, const int* __restrict__ steps, float* __restrict__ ws) {
+    const long long* __restrict__ seeds, const int* __restrict__ steps, float* __restrict__ ws,
+    const float* __restrict__ ln_min_p) {
   constexpr int NC = kSlices * kTopkMax / kSlThreads;   // candidates per thread
   __shared__ int s_off[kSlices + 1];
   __shared__ int s3[3 * (kSlThreads / 64)];
@@ -1007,7 +1136,20 @@ __global__ __launch_bounds__(kSlThreads) void samp_topk_kernel(
     }
     return;
   }
-  const uint32_t th = wg_kth_key<NC>(key, kk, s3);
+  uint32_t th = wg_kth_key<NC>(key, kk, s3);
+  if constexpr (MP) {
+    // min_p: entries below the threshold leave before Z, the above-masses, the ranks
+    // and the prefix sum, so they take no rank and no mass.  The row's max is among
+    // the candidates (it is the top-1 of its slice).
+    const float lnmp = ln_min_p[row];
+    if (lnmp > -INFINITY) {
+      uint32_t km = 0u;
+#pragma unroll
+      for (int j = 0; j < NC; ++j) km = max(km, key[j]);
+      km = wave_max_u32_wg(km, s3);
+      th = max(th, minp_key(key_to_f32(km), temperature[row], lnmp));
+    }
+  }
 #pragma unroll
   for (int j = 0; j < NC; ++j)
     if (key[j] >= th && key[j] > kNegInfKey) {
@@ -1083,14 +1225,37 @@ __global__ __launch_bounds__(kSlThreads) void samp_topk_kernel(
   }
 }
 
+__global__ __launch_bounds__(kSlThreads) void samp_topk_kernel(
+    int* __restrict__ out_tokens, int vocab, const float* __restrict__ temperature,
+    const float* __restrict__ top_p, const int* __restrict__ top_k,
+    const long long* __restrict__ seeds, const int* __restrict__ steps, float* __restrict__ ws) {
+  samp_topk_body<false>(out_tokens, vocab, temperature, top_p, top_k, seeds, steps, ws, nullptr);
+}
+
+__global__ __launch_bounds__(kSlThreads) void samp_topk_minp_kernel(
+    int* __restrict__ out_tokens, int vocab, const float* __restrict__ temperature,
+    const float* __restrict__ top_p, const int* __restrict__ top_k,
+    const long long* __restrict__ seeds, const int* __restrict__ steps, float* __restrict__ ws,
+    const float* __restrict__ ln_min_p) {
+  samp_topk_body<true>(out_tokens, vocab, temperature, top_p, top_k, seeds, steps, ws, ln_min_p);
+}
+
+#undef FT_SAMPLE_ARGS
+#undef FT_SAMPLE_PASS
+
 }  // namespace ft
 
 extern "C" int ft_sample_ws_floats() { return ft::kWsRow; }
 
+// ln_min_p: optional per-row fp32 ln(min_p), -inf = off for that row.  Null: exactly the
+// launches (kernels and arguments) of the sampler without min_p.  Non-null: the min_p
+// variants of the draw / top-k / one-workgroup kernels, and samp_minp_kernel between
+// the slice stats and the draw.
 extern "C" int ft_sample(int* out_tokens, const void* logits, int logits_is_bf16, long logit_stride,
                          int batch, int vocab, const float* temperature, const float* top_p,
                          const int* top_k, const long long* seeds, const int* steps,
-                         const uint32_t* allow_mask, int mask_words, float* ws, hipStream_t stream) {
+                         const uint32_t* allow_mask, int mask_words, float* ws,
+                         const float* ln_min_p, hipStream_t stream) {
   if (batch <= 0) return 0;
   if (vocab > ft::kSlots * ft::kSampThreads) return -3;
   if (vocab % 8 != 0 || logit_stride % 8 != 0) return -4;
@@ -1104,29 +1269,44 @@ extern "C" int ft_sample(int* out_tokens, const void* logits, int logits_is_bf16
       hipLaunchKernelGGL(ft::samp_stats_kernel<TT>, dim3(ft::kSlices, batch), dim3(ft::kSlThreads),\
                          0, stream, lg, logit_stride, vocab, temperature, top_k, allow_mask,     \
                          mask_words, ws);                                                        \
-      hipLaunchKernelGGL(ft::samp_draw_kernel<TT>, dim3(batch), dim3(ft::kSampThreads), 0, stream,\
-                         out_tokens, lg, logit_stride, vocab, temperature, top_p, top_k, seeds,  \
-                         steps, allow_mask, mask_words, ws);                                     \
+      if (ln_min_p != nullptr) {                                                                 \
+        hipLaunchKernelGGL(ft::samp_minp_kernel<TT>, dim3(ft::kSlices, batch),                   \
+                           dim3(ft::kSlThreads), 0, stream, lg, logit_stride, vocab, temperature,\
+                           top_k, allow_mask, mask_words, ln_min_p, ws);                         \
+        hipLaunchKernelGGL(ft::samp_draw_minp_kernel<TT>, dim3(batch), dim3(ft::kSampThreads), 0,\
+                           stream, out_tokens, lg, logit_stride, vocab, temperature, top_p,      \
+                           top_k, seeds, steps, allow_mask, mask_words, ws, ln_min_p);           \
+      } else {                                                                                   \
+        hipLaunchKernelGGL(ft::samp_draw_kernel<TT>, dim3(batch), dim3(ft::kSampThreads), 0,     \
+                           stream, out_tokens, lg, logit_stride, vocab, temperature, top_p,      \
+                           top_k, seeds, steps, allow_mask, mask_words, ws);                     \
+      }                                                                                          \
       hipLaunchKernelGGL(ft::samp_above_kernel<TT>, dim3(ft::kSlices, batch), dim3(ft::kSlThreads),\
                          0, stream, lg, logit_stride, vocab, temperature, allow_mask, mask_words, \
                          ws);                                                                    \
-      hipLaunchKernelGGL(ft::samp_topk_kernel, dim3(batch), dim3(ft::kSlThreads), 0, stream,     \
-                         out_tokens, vocab, temperature, top_p, top_k, seeds, steps, ws);        \
+      if (ln_min_p != nullptr) {                                                                 \
+        hipLaunchKernelGGL(ft::samp_topk_minp_kernel, dim3(batch), dim3(ft::kSlThreads), 0,      \
+                           stream, out_tokens, vocab, temperature, top_p, top_k, seeds, steps,   \
+                           ws, ln_min_p);                                                        \
+      } else {                                                                                   \
+        hipLaunchKernelGGL(ft::samp_topk_kernel, dim3(batch), dim3(ft::kSlThreads), 0, stream,   \
+                           out_tokens, vocab, temperature, top_p, top_k, seeds, steps, ws);      \
+      }                                                                                          \
       flags = reinterpret_cast<int*>(ws + ft::kWsFlag);                                          \
+    }                                                                                            \
+    if (ln_min_p != nullptr) {                                                                   \
+      hipLaunchKernelGGL(ft::sample_minp_kernel<TT>, dim3(batch), dim3(ft::kSampThreads), 0,     \
+                         stream, out_tokens, lg, logit_stride, vocab, temperature, top_p, top_k, \
+                         seeds, steps, allow_mask, mask_words, (const int*)flags, ft::kWsRow,    \
+                         ln_min_p);                                                              \
+    } else {                                                                                     \
+      hipLaunchKernelGGL(ft::sample_kernel<TT>, dim3(batch), dim3(ft::kSampThreads), 0, stream,  \
+                         out_tokens, lg, logit_stride, vocab, temperature, top_p, top_k, seeds,  \
+                         steps, allow_mask, mask_words, (const int*)flags, ft::kWsRow);          \
     }                                                                                            \
   }
   if (logits_is_bf16) FT_SAMPLE_ALL(uint16_t) else FT_SAMPLE_ALL(float)
 #undef FT_SAMPLE_ALL
-  dim3 grid(batch), block(ft::kSampThreads);
-  if (logits_is_bf16) {
-    hipLaunchKernelGGL(ft::sample_kernel<uint16_t>, grid, block, 0, stream, out_tokens,
-                       (const uint16_t*)logits, logit_stride, vocab, temperature, top_p, top_k,
-                       seeds, steps, allow_mask, mask_words, (const int*)flags, ft::kWsRow);
-  } else {
-    hipLaunchKernelGGL(ft::sample_kernel<float>, grid, block, 0, stream, out_tokens,
-                       (const float*)logits, logit_stride, vocab, temperature, top_p, top_k,
-                       seeds, steps, allow_mask, mask_words, (const int*)flags, ft::kWsRow);
-  }
   return static_cast<int>(hipGetLastError());
 }
 

@@ -141,6 +141,9 @@ class LLMEngine:
         # unfinished requests with SamplingParams.logprobs (runner.lp_active: steps scan
         # their rows for it only while there is one)
         self._lp_reqs: set = set()
+        # unfinished requests with SamplingParams.min_p > 0 (runner.mp_active: steps scan
+        # their rows for it only while there is one)
+        self._mp_reqs: set = set()
         # FT_PENALTY_VERIFY=1 (tests, debugging): a finishing sequence's slot is read back
         # and compared with the host's truth (_pen_verify)
         self.pen_verify = os.environ.get("FT_PENALTY_VERIFY", "0") == "1"
@@ -164,7 +167,12 @@ class LLMEngine:
             self._check_penalties(params)
         if params.logprobs is not None:
             self._check_logprobs(params)
+        if params.min_p > 0.0 and self.cfg.tp_size > 1:
+            raise EngineError("min_p is not supported with tensor parallelism yet")
         seq = Sequence(request_id, prompt_ids, params, on_output, meta)
+        if params.min_p > 0.0:
+            self._mp_reqs.add(request_id)
+            self.runner.mp_active = True
         if params.has_penalties:
             self._pen_reqs.add(request_id)
         if params.logprobs is not None:
@@ -931,6 +939,9 @@ class LLMEngine:
         if self._lp_reqs:
             self._lp_reqs.discard(seq.request_id)
             self.runner.lp_active = bool(self._lp_reqs)
+        if self._mp_reqs:
+            self._mp_reqs.discard(seq.request_id)
+            self.runner.mp_active = bool(self._mp_reqs)
         if seq.pen_slot >= 0:
             try:
                 if self.pen_verify and reason != "error":
@@ -1044,6 +1055,7 @@ class LLMEngine:
             "penalty_steps": int(getattr(self.runner, "stats", {}).get("penalty_steps", 0)),
             "logprob_steps": int(getattr(self.runner, "stats", {}).get("logprob_steps", 0)),
             "logprob_rows": int(getattr(self.runner, "stats", {}).get("logprob_rows", 0)),
+            "min_p_steps": int(getattr(self.runner, "stats", {}).get("min_p_steps", 0)),
             "swapped": len(self.scheduler.swapped),
             "swap_outs": self.scheduler.num_swap_out,
             "swap_ins": self.scheduler.num_swap_in,

@@ -24,6 +24,7 @@ from ..models.config import ModelConfig
 from ..models.llama import AttnMeta, LlamaModel
 from ..parallel.comm import SINGLE, TPComm
 from .config import EngineConfig
+from .sampling_params import ln_min_p
 from .scheduler import ScheduledBatch
 
 log = logging.getLogger("fasttalk.engine.runner")
@@ -70,6 +71,20 @@ def pen_words(mb: int) -> int:
     with a penalised row uploads them in the same copy (it starts 4 * mb words earlier)
     and a step without one uploads exactly what it always did."""
     return 4 * mb
+
+
+def minp_words(mb: int) -> int:
+    """fp32 words of a step's per-row ln(min_p) (-inf = off).  They sit between the penalty
+    prefix and the decode inputs (pen | min_p | inputs): a step with a min_p row starts
+    its one copy at them, a step with a penalised row at the penalty prefix as before
+    (which then carries them along), any other step uploads exactly what it always did."""
+    return mb
+
+
+def _gkey(nb: int, pen: bool, mp: bool = False):
+    """Key of a decode graph / split sampler graph variant: (bucket, pen), and (bucket,
+    pen, True) for the variant whose sampler reads the ln(min_p) array."""
+    return (nb, pen, True) if mp else (nb, pen)
 
 
 def _pen_views(buf: torch.Tensor, mb: int):
@@ -194,12 +209,15 @@ class _Staging:
         self.lp_want: Optional[np.ndarray] = None
         # one pinned int32 image, laid out like the device inputs (_input_views), so a
         # step's inputs go up in ONE copy: small | f32 | seeds (int64) | block tables
-        pw = pen_words(mb)
-        self.h_all = torch.zeros(pw + input_words(mb, max_blocks), dtype=i32, pin_memory=pin)
-        self.h_in = self.h_all[pw:]
+        pw, mw = pen_words(mb), minp_words(mb)
+        self.h_all = torch.zeros(pw + mw + input_words(mb, max_blocks), dtype=i32, pin_memory=pin)
+        self.h_in = self.h_all[pw + mw:]
         self.h_pen = tuple(v.numpy() for v in _pen_views(self.h_all, mb))
         self.h_pen[0][:] = -1
         self.pen = False   # the staged step has a penalised row
+        self.h_minp = self.h_all[pw:pw + mw].view(torch.float32).numpy()   # ln(min_p) per row
+        self.h_minp[:] = -np.inf
+        self.mp = False    # the staged step has a min_p row
         self.h_small, self.h_f32, self.h_seeds, self.h_bt = _input_views(self.h_in, mb, max_blocks)
         self.h_out = torch.zeros(mb, dtype=i32, pin_memory=pin)
         self.h_err = torch.zeros(1, dtype=i32, pin_memory=pin)  # TP collective error flag
@@ -364,11 +382,16 @@ class ModelRunner:
         # int32 fields: ids | pos | slots | seq_lens | top_k | steps, then temperature |
         # top_p (f32), seeds (int64), block tables
         # (the penalty prefix in front of them is uploaded only by steps that use it)
-        pw = pen_words(mb)
-        self.d_all = torch.zeros(pw + input_words(mb, self.max_blocks_per_seq), dtype=i32, device=dv)
-        self.d_in = self.d_all[pw:]
+        pw, mw = pen_words(mb), minp_words(mb)
+        self.d_all = torch.zeros(pw + mw + input_words(mb, self.max_blocks_per_seq), dtype=i32,
+                                 device=dv)
+        self.d_in = self.d_all[pw + mw:]
         self.d_pen = _pen_views(self.d_all, mb)
         self.d_pen[0].fill_(-1)
+        # ln(min_p) per row (-inf = off): read only by the min_p graph variants
+        self.d_minp = self.d_all[pw:pw + mw].view(torch.float32)
+        self.d_minp.fill_(float("-inf"))
+        self.mp_active = False   # the engine holds an unfinished request with min_p > 0
         self.d_small, self.d_f32, self.d_seeds, self.d_bt = _input_views(self.d_in, mb, self.max_blocks_per_seq)
         self.d_input_ids = self.d_small[0:mb]
         self.d_positions = self.d_small[mb:2 * mb]
@@ -456,7 +479,8 @@ class ModelRunner:
         self._blk_event = torch.cuda.Event() if self._blk_host is not None else None
         self._blk_armed = False
         self._blk_waits = 0
-        # keyed (batch bucket, pen): pen = the sampler is wrapped in the penalty kernels
+        # keyed (batch bucket, pen): pen = the sampler is wrapped in the penalty kernels;
+        # (batch bucket, pen, True): the sampler also reads the ln(min_p) array (_gkey)
         self.graphs: Dict[Tuple[int, bool], torch.cuda.CUDAGraph] = {}
         # guided decoding, pipelined: per bucket a forward graph (-> logits) and a
         # sampler graph, so the next step's forward is queued before this step's
@@ -486,7 +510,8 @@ class ModelRunner:
             if comm.world_size > 1 else 0
         self._trace_tp = os.environ.get("FT_TP_TRACE", "0") == "1" and comm.world_size > 1
         self.stats = {"graph_replays": 0, "eager_decode": 0, "prefill_steps": 0, "captures": 0,
-                      "penalty_steps": 0, "logprob_steps": 0, "logprob_rows": 0}
+                      "penalty_steps": 0, "logprob_steps": 0, "logprob_rows": 0,
+                      "min_p_steps": 0}
         # tests: a list here collects every step's logits (fp32; eager steps on the host,
         # graph-replayed and mixed-ahead steps as stream-ordered device copies) -- TP-vs-TP=1
         # numerics are compared on logits, not on greedy tokens of random weights.  With
@@ -681,17 +706,37 @@ class ModelRunner:
             torch.cuda.synchronize(self.device)
         return self.pen_table[slot].cpu().numpy().view(np.uint16)
 
+    def _minp_array(self, seqs) -> Optional[np.ndarray]:
+        """ln(min_p) (fp32, -inf = off) of a step's sampled rows, or None when no row has
+        min_p (the step then uploads and launches what it always did)."""
+        if not self.mp_active:
+            return None
+        a = None
+        for i, s in enumerate(seqs):
+            v = s.params.min_p
+            if v > 0.0 and s.params.temperature > 0.0:
+                if a is None:
+                    a = np.full(len(seqs), -np.inf, np.float32)
+                a[i] = ln_min_p(v)
+        return a
+
     def _pen_sample(self, logits, samp, dmask, pen, out=None):
         """The sampler over ``logits`` (raw: they are left untouched), wrapped in the
-        penalty kernels when ``pen`` (device slot, rep, pres, freq) is given."""
-        temp, topp, topk, seeds, steps = samp
+        penalty kernels when ``pen`` (device slot, rep, pres, freq) is given.  ``samp``:
+        the five device sampling arrays, and the step's ln(min_p) array as a sixth when
+        one of its rows has min_p."""
+        temp, topp, topk, seeds, steps = samp[:5]
+        mp = samp[5] if len(samp) > 5 else None
+        if mp is not None:
+            self.stats["min_p_steps"] += 1
         if pen is None:
-            return ops.sample(logits, temp, topp, topk, seeds, steps, out=out, mask=dmask)
+            return ops.sample(logits, temp, topp, topk, seeds, steps, out=out, mask=dmask,
+                              min_p=mp)
         self.stats["penalty_steps"] += 1
         slot, rp, pr, fr = pen
         pl = ops.penalty_apply(logits, slot, rp, pr, fr, self.pen_table, self.pen_bias_ids,
                                self.pen_bias_vals, out=torch.empty_like(logits))
-        out = ops.sample(pl, temp, topp, topk, seeds, steps, out=out, mask=dmask)
+        out = ops.sample(pl, temp, topp, topk, seeds, steps, out=out, mask=dmask, min_p=mp)
         ops.penalty_update(self.pen_table, slot, out[:logits.shape[0]])
         return out
 
@@ -812,6 +857,7 @@ class ModelRunner:
         host["sampling"] = self._sampling_arrays(sseqs)
         host["pen"] = self._pen_arrays(sseqs)
         host["lp"] = self._lp_arrays(sseqs)
+        host["minp"] = self._minp_array(sseqs)
         if self.logits_tap_ids is not None:
             self._tap_rows = [s.request_id for s in sseqs]
         return host
@@ -844,11 +890,14 @@ class ModelRunner:
         arrays = [host[k] for k in names]
         has_logits = len(host["lrows"]) > 0
         pen = host.get("pen") if has_logits else None
+        minp = host.get("minp") if has_logits else None
         if has_logits:
             arrays += list(host["sampling"])
             if masks is not None:
                 arrays.append(masks)
-            if pen is not None:   # same upload as the other sampling arrays
+            if minp is not None:   # same upload as the other sampling arrays
+                arrays.append(minp)
+            if pen is not None:
                 arrays += list(pen)
         if self.is_gpu:
             dev = self._upload(arrays)
@@ -882,8 +931,10 @@ class ModelRunner:
                     self._comm_fault()
             return []
         k = len(names)
-        samp = dev[k:k + 5]
+        samp = list(dev[k:k + 5])
         dmask = dev[k + 5] if masks is not None else None
+        if minp is not None:
+            samp.append(dev[k + 5 + (masks is not None)])
         dpen = dev[-4:] if pen is not None else None
         return self._sample(h, host["sampling"], masks, dev_sampling=samp, dev_mask=dmask,
                             dev_pen=dpen, lp_want=host.get("lp"))
@@ -1085,12 +1136,13 @@ class ModelRunner:
                                        "rowmap": gather}, masks))
         self._set_masks(masks, n)
         pen = st.pen
-        self._decode_enqueue(st, nb, n, from_device=bool(ahead), gather=gather, pen=pen)
-        if self.logits_tap is not None and (nb, pen) in self._graph_logits:
+        self._decode_enqueue(st, nb, n, from_device=bool(ahead), gather=gather, pen=pen, mp=st.mp)
+        gk = _gkey(nb, pen, st.mp)
+        if self.logits_tap is not None and gk in self._graph_logits:
             # copied in stream order: the next queued replay overwrites the graph's logits
             if self.logits_tap_ids is not None:
                 self._tap_rows = [s.request_id for s in seqs]
-            self._tap(self._graph_logits[(nb, pen)][:n].float().clone())
+            self._tap(self._graph_logits[gk][:n].float().clone())
         return DecodeHandle(st, n, nb)
 
     @torch.inference_mode()
@@ -1103,6 +1155,7 @@ class ModelRunner:
         if isinstance(h, MixedHandle):
             assert h.pending
             pen = self._pen_arrays(h.seqs) if h.seqs is not None else None
+            # (a min_p array went up with the step's sampling arrays: it is in h.samp)
             arrays = ([masks] if masks is not None else []) + list(pen or ())
             dev = []
             if arrays:
@@ -1118,13 +1171,18 @@ class ModelRunner:
         # the rows' penalty slots as they stand now (a lazy grammar that bound meanwhile
         # has given its slot back): staged and uploaded with this sampler, not the forward
         pen = self._pen_arrays(h.seqs) if h.seqs is not None else None
+        pw = pen_words(self.max_decode_batch)
+        mw = minp_words(self.max_decode_batch) if st.mp else 0   # staged by _decode_fill
         if pen is not None:
             self._pen_stage(st, pen, h.n, h.nb)
-            pw = pen_words(self.max_decode_batch)
-            self.d_all[:pw].copy_(st.h_all[:pw], non_blocking=True)
+            self.d_all[:pw + mw].copy_(st.h_all[:pw + mw], non_blocking=True)
             self.stats["penalty_steps"] += 1
-        key = (h.nb, pen is not None)
-        pair = self.graphs_split.get(key) or self._capture_split(h.nb, pen is not None)
+        elif mw:
+            self.d_all[pw:pw + mw].copy_(st.h_all[pw:pw + mw], non_blocking=True)
+        if mw:
+            self.stats["min_p_steps"] += 1
+        key = _gkey(h.nb, pen is not None, st.mp)
+        pair = self.graphs_split.get(key) or self._capture_split(h.nb, pen is not None, st.mp)
         pair[1].replay()
         self._pending_split = None
         want = self._lp_arrays(h.seqs) if h.seqs is not None else None
@@ -1211,6 +1269,7 @@ class ModelRunner:
         if nd:
             names += ["d_bt", "d_sl"]
         arrays = [host[k] for k in names] + list(host["sampling"])
+        minp = host["minp"]
         # rowmap[i] < 0: row i's sequence has no queued step (it joined after the last
         # queued step was built); its id is its last token, already in host["ids"]
         rm = np.asarray(rowmap if rowmap is not None else [], dtype=np.int64)
@@ -1220,6 +1279,8 @@ class ModelRunner:
         arrays.append(dst if partial and len(dst) else np.zeros(1, np.int64))
         if masks is not None and not defer_sample:
             arrays.append(masks)
+        if minp is not None:   # does not depend on the masks: also with a deferred sampler
+            arrays.append(minp)
         # a deferred sampler reads its rows' penalty slots when it is queued (sample_launch):
         # whether a lazy grammar bound is known only then
         pen = None if defer_sample else host["pen"]
@@ -1265,7 +1326,9 @@ class ModelRunner:
         if self.logits_tap is not None:
             self._tap(logits.float().cpu())   # taps are host tensors (tests)
         n = logits.shape[0]
-        samp = dev[len(names):len(names) + 5]
+        samp = list(dev[len(names):len(names) + 5])
+        if minp is not None:
+            samp.append(dev[len(names) + 7 + (masks is not None and not defer_sample)])
         if mh.host.shape[0] < n:
             mh.host = torch.zeros(2 * n, dtype=torch.int32, pin_memory=self.is_gpu)
         mh.n = n
@@ -1340,6 +1403,16 @@ class ModelRunner:
         st.hf[:n] = temp
         st.hf[mb:mb + n] = topp
         st.hseed[:n] = seeds
+        # ln(min_p): every step writes its rows' words (-inf = off), so a replay of the
+        # min_p variant never sees a stale value
+        st.h_minp[:nb] = -np.inf
+        st.mp = False
+        if self.mp_active:
+            for i, s in enumerate(seqs):
+                v = s.params.min_p
+                if v > 0.0 and temp[i] > 0.0:
+                    st.h_minp[i] = ln_min_p(v)
+                    st.mp = True
         if nb > n:  # padding rows: no KV write, empty context (no attention work), greedy
             ids[n:nb] = 0
             pos[n:nb] = 0
@@ -1399,16 +1472,21 @@ class ModelRunner:
 
     def _decode_enqueue(self, st: "_Staging", nb: int, n: int, from_device: bool = False,
                         gather: Optional[np.ndarray] = None, fwd_only: bool = False,
-                        pen: bool = False):
+                        pen: bool = False, mp: bool = False):
         nw = 10 * self.max_decode_batch + nb * self.max_blocks_per_seq
         if self._gaps is not None:   # g: a split step, closed by its sampler (sample_launch)
             self._gap_mark(True, "g" if fwd_only else "d")
-        if pen:   # the same copy, started at the penalty prefix
-            pw = pen_words(self.max_decode_batch)
+        if pen:   # the same copy, started at the penalty prefix (it carries the min_p words)
+            pw = pen_words(self.max_decode_batch) + minp_words(self.max_decode_batch)
             self.d_all[:pw + nw].copy_(st.h_all[:pw + nw], non_blocking=True)
             self.stats["penalty_steps"] += 1
+        elif mp and not fwd_only:   # the same copy, started at the min_p words
+            pw, mw = pen_words(self.max_decode_batch), minp_words(self.max_decode_batch)
+            self.d_all[pw:pw + mw + nw].copy_(st.h_all[pw:pw + mw + nw], non_blocking=True)
         else:
             self.d_in[:nw].copy_(st.h_in[:nw], non_blocking=True)
+        if mp and not fwd_only:
+            self.stats["min_p_steps"] += 1
         if from_device:  # the previous step's sampled ids feed this step
             if gather is None:
                 self.d_input_ids[:nb].copy_(self.d_out[:nb])
@@ -1427,20 +1505,21 @@ class ModelRunner:
                     self.d_input_ids.index_copy_(0, self.d_map[k:2 * k],
                                                  self.d_out.index_select(0, self.d_map[:k]))
         if fwd_only:
-            pair = self.graphs_split.get((nb, False)) or self.graphs_split.get((nb, True))
+            pair = self._split_any(nb)   # every variant of a bucket shares the forward graph
             if pair is None:
                 pair = self._capture_split(nb, False)
             pair[0].replay()
             self.stats["graph_replays"] += 1
             self.stats["deferred_samples"] = self.stats.get("deferred_samples", 0) + 1
             return
-        g = self.graphs.get((nb, pen))
+        gk = _gkey(nb, pen, mp)
+        g = self.graphs.get(gk)
         if g is None:
-            g = self._capture(nb, pen)
+            g = self._capture(nb, pen, mp)
         g.replay()
         self.stats["graph_replays"] += 1
         if st.lp_want is not None:   # on the graph's raw logits, before the next replay overwrites them
-            self._lp_launch(st.lp, st.lp_want, self._graph_logits[(nb, pen)], self.d_out)
+            self._lp_launch(st.lp, st.lp_want, self._graph_logits[gk], self.d_out)
         st.h_out[:n].copy_(self.d_out[:n], non_blocking=True)
         flag = self.comm.error_flag if self.checks_comm else None
         st.err_armed = flag is not None
@@ -1502,43 +1581,48 @@ class ModelRunner:
                         dec_block_tables=self.d_bt[:nb], dec_seq_lens=self.d_seq_lens[:nb],
                         tmp_out=self.tmp_out, tmp_ml=self.tmp_ml, dec_counters=self.dec_counters)
 
-    def _graph_sample(self, logits, nb: int, pen: bool):
+    def _split_any(self, nb: int):
+        return next((v for k, v in self.graphs_split.items() if k[0] == nb), None)
+
+    def _graph_sample(self, logits, nb: int, pen: bool, mp: bool = False):
         """The sampler of a decode graph: with ``pen`` it is apply -> sample -> update,
-        the penalties applied out of place so the graph's logits stay raw (logit taps)."""
+        the penalties applied out of place so the graph's logits stay raw (logit taps);
+        with ``mp`` the sampler reads the step's ln(min_p) array."""
         mask = self.d_mask[:nb] if self.d_mask is not None else None
         if pen:
             slot, rp, pr, fr = (t[:nb] for t in self.d_pen)
             logits = ops.penalty_apply(logits, slot, rp, pr, fr, self.pen_table, self.pen_bias_ids,
                                        self.pen_bias_vals, out=torch.empty_like(logits))
         ops.sample(logits, self.d_temp[:nb], self.d_top_p[:nb], self.d_top_k[:nb],
-                   self.d_seeds[:nb], self.d_steps[:nb], out=self.d_out[:nb], mask=mask)
+                   self.d_seeds[:nb], self.d_steps[:nb], out=self.d_out[:nb], mask=mask,
+                   min_p=self.d_minp[:nb] if mp else None)
         if pen:
             ops.penalty_update(self.pen_table, slot, self.d_out[:nb])
 
-    def _graph_body(self, nb: int, keep: bool = False, pen: bool = False):
+    def _graph_body(self, nb: int, keep: bool = False, pen: bool = False, mp: bool = False):
         meta = self._decode_meta(nb)
         h = self.model.forward(self.d_input_ids[:nb], meta, self.kv)
         logits = self.model.compute_logits(h)
         if keep:   # graph-pool memory: holds each replay's logits until the next one
-            self._graph_logits[(nb, pen)] = logits
-        self._graph_sample(logits, nb, pen)
+            self._graph_logits[_gkey(nb, pen, mp)] = logits
+        self._graph_sample(logits, nb, pen, mp)
         if self.checks_comm:
             self.comm.export_error()
 
     @torch.inference_mode()
-    def _capture_split(self, nb: int, pen: bool = False):
+    def _capture_split(self, nb: int, pen: bool = False, mp: bool = False):
         """The forward graph (-> logits, held in ``_fwd_logits``) and the sampler graph
         of bucket ``nb`` for pipelined guided decoding, captured like ``_capture``.
-        The two ``pen`` variants share the forward graph; only the sampler is captured
-        again (with the penalty kernels around it).
+        The ``pen`` / ``mp`` variants share the forward graph; only the sampler is captured
+        again (with the penalty kernels around it, reading the ln(min_p) array).
         Nothing replays between a step's two halves (its sampler is queued before
         the next forward), so the pool may share their temporaries with every other
         graph; the logits stay allocated."""
         t0 = time.time()
-        other = self.graphs_split.get((nb, not pen))
+        other = self._split_any(nb)
         if other is not None:
             # (a forward may be pending here: only the sampler runs, on its own logits)
-            return self._capture_split_sampler(nb, pen, other[0], t0)
+            return self._capture_split_sampler(nb, pen, other[0], t0, mp)
         self._assert_no_pending_split("split-graph capture")
         saved = (self.d_slots[:nb].clone(), self.d_seq_lens[:nb].clone())
         self.d_slots[:nb].fill_(-1)
@@ -1550,7 +1634,7 @@ class ModelRunner:
             return self.model.compute_logits(h)
 
         def samp(lg):
-            self._graph_sample(lg, nb, pen)
+            self._graph_sample(lg, nb, pen, mp)
 
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
@@ -1569,26 +1653,28 @@ class ModelRunner:
         self.d_slots[:nb].copy_(saved[0])
         self.d_seq_lens[:nb].copy_(saved[1])
         self._pen_capture_end(nb, psaved)
-        self.graphs_split[(nb, pen)] = (gf, gs)
+        self.graphs_split[_gkey(nb, pen, mp)] = (gf, gs)
         self.stats["captures"] += 1
-        log.info("captured split decode graphs batch=%d pen=%d in %.2fs", nb, pen, time.time() - t0)
+        log.info("captured split decode graphs batch=%d pen=%d min_p=%d in %.2fs", nb, pen, mp,
+                 time.time() - t0)
         return gf, gs
 
-    def _capture_split_sampler(self, nb: int, pen: bool, gf, t0: float):
+    def _capture_split_sampler(self, nb: int, pen: bool, gf, t0: float, mp: bool = False):
         lg = self._fwd_logits[nb]
         psaved = self._pen_capture_begin(nb, pen)
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            self._graph_sample(lg, nb, pen)  # warm-up (allocator)
+            self._graph_sample(lg, nb, pen, mp)  # warm-up (allocator)
         torch.cuda.current_stream(self.device).wait_stream(s)
         gs = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gs, pool=self.graph_pool):
-            self._graph_sample(lg, nb, pen)
+            self._graph_sample(lg, nb, pen, mp)
         self._pen_capture_end(nb, psaved)
-        self.graphs_split[(nb, pen)] = (gf, gs)
+        self.graphs_split[_gkey(nb, pen, mp)] = (gf, gs)
         self.stats["captures"] += 1
-        log.info("captured split sampler graph batch=%d pen=%d in %.2fs", nb, pen, time.time() - t0)
+        log.info("captured split sampler graph batch=%d pen=%d min_p=%d in %.2fs", nb, pen, mp,
+                 time.time() - t0)
         return gf, gs
 
     def _pen_capture_begin(self, nb: int, pen: bool):
@@ -1605,7 +1691,7 @@ class ModelRunner:
             self.d_pen[0][:nb].copy_(saved)
 
     @torch.inference_mode()
-    def _capture(self, nb: int, pen: bool = False):
+    def _capture(self, nb: int, pen: bool = False, mp: bool = False):
         """Captures the decode graph of batch bucket ``nb``.  Always under
         inference mode, whichever path triggers it (pipelined launches run outside
         ``execute``): the CUDA generator's graph-safe RNG state is created by the
@@ -1620,19 +1706,20 @@ class ModelRunner:
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s), self._long_waits():
-            self._graph_body(nb, pen=pen)  # warm-up (allocator, lazy init)
+            self._graph_body(nb, pen=pen, mp=mp)  # warm-up (allocator, lazy init)
         torch.cuda.current_stream(self.device).wait_stream(s)
         if self.graph_pool is None:
             self.graph_pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self.graph_pool):
-            self._graph_body(nb, keep=True, pen=pen)
+            self._graph_body(nb, keep=True, pen=pen, mp=mp)
         self.d_slots[:nb].copy_(saved[0])
         self.d_seq_lens[:nb].copy_(saved[1])
         self._pen_capture_end(nb, psaved)
-        self.graphs[(nb, pen)] = g
+        self.graphs[_gkey(nb, pen, mp)] = g
         self.stats["captures"] += 1
-        log.info("captured decode graph batch=%d pen=%d in %.2fs", nb, pen, time.time() - t0)
+        log.info("captured decode graph batch=%d pen=%d min_p=%d in %.2fs", nb, pen, mp,
+                 time.time() - t0)
         return g
 
     def _decode_eager(self, seqs, masks) -> List[int]:

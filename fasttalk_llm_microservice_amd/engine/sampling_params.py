@@ -5,6 +5,7 @@ backends: temperature / max_tokens / top_p / stop (vLLM,
 from __future__ import annotations
 
 import dataclasses
+import math
 import random
 from typing import Any, List, Optional
 
@@ -46,6 +47,22 @@ def pick_logprobs(src) -> Optional[int]:
     return top
 
 
+def pick_min_p(src) -> dict:
+    """``min_p`` of a request dict (an OpenAI body, a WebSocket session config) as
+    SamplingParams keywords: empty when the request does not set it.  Validated: raises
+    ValueError like SamplingParams does."""
+    v = src.get("min_p")
+    if v is None:
+        return {}
+    return {"min_p": SamplingParams(min_p=v).min_p}
+
+
+def ln_min_p(min_p: float) -> float:
+    """What the sampler takes for ``min_p``: ln(min_p) computed in float64 (rounded once
+    to fp32 where it is stored), -inf for 0 = off."""
+    return math.log(min_p) if min_p > 0.0 else float("-inf")
+
+
 @dataclasses.dataclass
 class SamplingParams:
     temperature: float = 0.7
@@ -79,8 +96,20 @@ class SamplingParams:
     # allow-mask, temperature, top-k and top-p; vLLM's default): None = off, 0..20 = the
     # sampled token's logprob plus that many most likely alternatives
     logprobs: Optional[int] = None
+    # vLLM / Ollama ``min_p`` in [0, 1], 0 = off: after the processors above, the
+    # allow-mask and temperature, before top-k / top-p, a token is kept iff
+    # p(token) >= min_p * p_max (ops/reference.py sample).  Greedy rows ignore it.
+    min_p: float = 0.0
 
     MAX_LOGIT_BIAS = 300
+
+    def _check_min_p(self):
+        v = self.min_p
+        if v is None:
+            v = 0.0
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:
+            raise ValueError("min_p must be a number in [0, 1]")
+        self.min_p = float(v)
 
     def _check_logprobs(self):
         v = self.logprobs
@@ -131,6 +160,7 @@ class SamplingParams:
     def __post_init__(self):
         self._check_penalties()
         self._check_logprobs()
+        self._check_min_p()
         if self.temperature is None:
             self.temperature = 0.7
         if self.temperature < 0:

@@ -353,14 +353,26 @@ def build_prefill_tiles(q_lens, tile_tokens: int, seq_lens=None, nkv: int = 8, n
 # sampling
 # ---------------------------------------------------------------------------------
 
-def sample(logits, temperature, top_p, top_k, seeds, steps, out=None, mask=None):
+def sample(logits, temperature, top_p, top_k, seeds, steps, out=None, mask=None, min_p=None):
+    """Fused sampler (csrc/kernels/sampling.hip; ops/reference.py ``sample`` on the CPU).
+
+    ``min_p``: None, or a per-row fp32 tensor that holds **ln(min_p)**, not min_p itself:
+    ``-inf`` switches a row off, ``0.0`` (min_p = 1) keeps only the maximal logits.
+    Compute it on the host in float64 and round once to fp32 (engine
+    ``sampling_params.ln_min_p``).  A row with ``temperature > 0`` keeps a token iff
+    ``float(bf16(x)) >= M + temperature * ln(min_p)``, M the row's largest allowed
+    bf16-rounded logit; top-k and top-p then work on the kept set.  With ``None`` the
+    launches are exactly those of the sampler without min_p."""
     if logits.is_cuda:
         b = logits.shape[0]
         if out is None:
             out = torch.empty(b, dtype=torch.int32, device=logits.device)
-        native().sample(out, logits, temperature, top_p, top_k, seeds, steps, mask)
+        if min_p is None:
+            native().sample(out, logits, temperature, top_p, top_k, seeds, steps, mask)
+        else:
+            native().sample(out, logits, temperature, top_p, top_k, seeds, steps, mask, min_p)
         return out
-    r = ref.sample(logits, temperature, top_p, top_k, seeds, steps, mask)
+    r = ref.sample(logits, temperature, top_p, top_k, seeds, steps, mask, min_p)
     if out is not None:
         out[: r.shape[0]].copy_(r)
         return out

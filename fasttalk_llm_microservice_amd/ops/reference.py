@@ -265,13 +265,24 @@ def token_logprobs(logits: torch.Tensor, sampled, want, out_lp: Optional[torch.T
 
 
 def sample(logits: torch.Tensor, temperature, top_p, top_k, seeds, steps,
-           mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+           mask: Optional[torch.Tensor] = None,
+           min_p: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Reference sampler (CPU backend).  Same contract as the HIP kernel:
     temperature <= 0 -> argmax (lowest id on ties); else top-k, then top-p over
     the survivors, then a draw from the renormalised distribution.  The draw is
     seeded by (seed, step) so it is reproducible, but it does not reproduce the
-    kernel's random stream bit for bit (tests compare distributions)."""
+    kernel's random stream bit for bit (tests compare distributions).
+
+    ``min_p``: None, or per-row fp32 **ln(min_p)** (-inf = off).  When given, the
+    logits are first rounded to bf16, as the kernels see them, and a row with
+    temperature > 0 and a finite entry keeps a token iff
+    ``x >= M + temperature * ln(min_p)``: M the largest allowed logit, the product and
+    the sum each rounded to fp32.  Top-k is unaffected by the order (the result is
+    top-k n kept); top-p takes its nucleus over the kept set, renormalised."""
     x = logits.float().clone()
+    if min_p is not None:
+        x = logits.bfloat16().float().clone()
+        min_p = torch.as_tensor(min_p, dtype=torch.float32).reshape(-1).cpu()
     b, v = x.shape
     if mask is not None:
         bits = mask[:b].to(torch.int64) & 0xFFFFFFFF
@@ -291,6 +302,9 @@ def sample(logits: torch.Tensor, temperature, top_p, top_k, seeds, steps,
         if 0 < k < v:
             kth = torch.topk(row, k).values[-1]
             keep &= row >= kth
+        if min_p is not None and float(min_p[i]) > float("-inf"):
+            t32 = torch.tensor(t, dtype=torch.float32)
+            keep &= row >= row.max() + t32 * min_p[i]   # fp32: product, then sum
         p = float(top_p[i])
         if p < 1.0:
             pr = torch.softmax(z.masked_fill(~keep, float("-inf")), dim=-1)
