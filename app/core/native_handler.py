@@ -329,12 +329,13 @@ class NativeHandler:
     # ------------------------------------------------------------------ generation
     def _params(self, temperature, max_tokens, top_p, top_k=None, stop=None, seed=None,
                 guided=None, ignore_eos=False, min_tokens=0, guided_lazy=False, priority=0,
-                penalties=None, logprobs=None):
+                penalties=None, logprobs=None, prompt_logprobs=None):
         """``penalties``: repetition_penalty / presence_penalty / frequency_penalty /
         logit_bias (engine.sampling_params.pick_penalties), and ``min_p`` (pick_min_p),
         which travels with them; the service defaults (DEFAULT_REPETITION_PENALTY ...,
         DEFAULT_MIN_P) fill in what a request leaves out.
-        ``logprobs``: SamplingParams.logprobs (pick_logprobs), None = off."""
+        ``logprobs``: SamplingParams.logprobs (pick_logprobs), None = off;
+        ``prompt_logprobs``: SamplingParams.prompt_logprobs (pick_prompt_logprobs)."""
         from fasttalk_llm_microservice_amd.engine.sampling_params import SamplingParams
 
         pen = {k: v for k, v in self.default_penalties.items()}
@@ -347,7 +348,7 @@ class NativeHandler:
             max_tokens=int(max_tokens or self.default_max_tokens),
             stop=stop, seed=seed, guided=guided, ignore_eos=ignore_eos, min_tokens=min_tokens,
             guided_lazy=bool(guided_lazy and guided is not None), priority=int(priority),
-            logprobs=logprobs, **pen)
+            logprobs=logprobs, prompt_logprobs=prompt_logprobs, **pen)
 
     async def stream_events(self, messages: List[Dict[str, Any]], temperature: Optional[float] = None,
                             max_tokens: Optional[int] = None, top_p: Optional[float] = None,
@@ -358,16 +359,19 @@ class NativeHandler:
                             min_tokens: int = 0, prefix_session: Optional[str] = None,
                             assistant_prefix: str = "", guided_lazy: bool = False,
                             priority: int = 0, penalties: Optional[Dict[str, Any]] = None,
-                            logprobs: Optional[int] = None) -> AsyncIterator[Any]:
+                            logprobs: Optional[int] = None,
+                            prompt_logprobs: Optional[int] = None) -> AsyncIterator[Any]:
         """``prefix_session`` (with ``session_id=None``): build the prompt on that
         session's token stream without making this request the session's turn.
         ``assistant_prefix``: text the assistant turn starts with (written into the
         prompt; the output stream holds only what follows it).  ``priority``: > 0
         prefills ahead of waiting prompts of lower priority.  ``logprobs``: every event's
-        ``logprobs`` then holds one entry per id of its ``token_ids``."""
+        ``logprobs`` then holds one entry per id of its ``token_ids``.  ``prompt_logprobs``:
+        the first event's ``prompt_logprobs`` then holds one entry per prompt token."""
         mt = int(max_tokens or self.default_max_tokens)
         params = self._params(temperature, mt, top_p, top_k, stop, seed, guided, ignore_eos,
-                              min_tokens, guided_lazy, priority, penalties, logprobs)
+                              min_tokens, guided_lazy, priority, penalties, logprobs,
+                              prompt_logprobs)
         if prompt_ids is None:
             if session_id is None and prefix_session is not None:
                 prompt_ids = self.build_prompt(messages, mt, prefix_session, tools, remember=False)

@@ -44,6 +44,10 @@ int ft_sample(int* out_tokens, const void* logits, int logits_is_bf16, long logi
 int ft_sample_ws_floats();
 int ft_logprobs_max();
 int ft_logprobs_ws_words();
+int ft_prompt_logprobs_ws_words();
+int ft_prompt_logprobs(const void* logits, int is_bf16, long stride, int rows, int vocab,
+                       const int* targets, const int* want, void* ws, float* out_lp, int* out_id,
+                       int* out_rank, hipStream_t stream);
 int ft_logprobs(const void* logits, int is_bf16, long stride, int rows, int vocab, const int* sampled,
                 const int* want, void* ws, float* out_lp, int* out_id, hipStream_t stream);
 int ft_penalty_max_bias();
@@ -527,6 +531,40 @@ void logprobs(at::Tensor logits, at::Tensor sampled, at::Tensor want, at::Tensor
                        sampled.data_ptr<int>(), want.data_ptr<int>(), ws.data_ptr(),
                        out_lp.data_ptr<float>(), out_id.data_ptr<int>(), cur_stream()),
            "logprobs");
+}
+
+// prompt logprobs (csrc/kernels/logprobs.hip, ft_prompt_logprobs): as logprobs() with the
+// given targets int32 [>= B] in place of the sampled ids, plus out_rank int32 [>= B]
+void prompt_logprobs(at::Tensor logits, at::Tensor targets, at::Tensor want, at::Tensor out_lp,
+                     at::Tensor out_id, at::Tensor out_rank) {
+  check_dev(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits [B, V] with contiguous rows");
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(is_bf16 || logits.scalar_type() == at::kFloat, "logits fp32 or bf16");
+  const int rows = (int)logits.size(0), vocab = (int)logits.size(1);
+  TORCH_CHECK((rows <= 1 || logits.stride(0) % 8 == 0) &&
+                  reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "logits rows must start 16-B aligned (row stride a multiple of 8)");
+  check_i32(targets, "targets");
+  check_i32(want, "want");
+  TORCH_CHECK(targets.numel() >= rows && want.numel() >= rows, "targets / want length");
+  const int64_t cols = 1 + ft_logprobs_max();
+  check_dev(out_lp, "out_lp");
+  check_i32(out_id, "out_id");
+  check_i32(out_rank, "out_rank");
+  TORCH_CHECK(out_lp.scalar_type() == at::kFloat && out_lp.is_contiguous() && out_lp.dim() == 2 &&
+                  out_id.dim() == 2 && out_lp.size(1) == cols && out_id.size(1) == cols &&
+                  out_lp.size(0) >= rows && out_id.size(0) >= rows,
+              "out_lp fp32 / out_id int32 [B, ", cols, "]");
+  TORCH_CHECK(out_rank.numel() >= rows, "out_rank int32 [B]");
+  at::Tensor ws = at::empty({(int64_t)rows * ft_prompt_logprobs_ws_words()},
+                            logits.options().dtype(at::kLong));   // stream-ordered scratch
+  const long stride = rows > 1 ? (long)logits.stride(0) : (long)((vocab + 7) / 8 * 8);
+  check_rc(ft_prompt_logprobs(logits.data_ptr(), is_bf16 ? 1 : 0, stride, rows, vocab,
+                              targets.data_ptr<int>(), want.data_ptr<int>(), ws.data_ptr(),
+                              out_lp.data_ptr<float>(), out_id.data_ptr<int>(),
+                              out_rank.data_ptr<int>(), cur_stream()),
+           "prompt_logprobs");
 }
 
 void kv_block_copy(at::Tensor k_cache, at::Tensor v_cache, at::Tensor src_dst) {
@@ -1160,6 +1198,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("penalty_seed", &penalty_seed);
   m.def("penalty_max_bias", []() { return (int64_t)ft_penalty_max_bias(); });
   m.def("logprobs", &logprobs);
+  m.def("prompt_logprobs", &prompt_logprobs);
   m.def("logprobs_max", []() { return (int64_t)ft_logprobs_max(); });
   m.def("kv_block_copy", &kv_block_copy);
   m.def("kv_swap", &kv_swap, py::arg("ptrs"), py::arg("ids"), py::arg("staging"),

@@ -184,6 +184,7 @@ enum FtCheckCode : int {
   kCkPenSlot = 7,      // penalties: state slot >= max_num_seqs
   kCkPenToken = 8,     // penalties: sampled / seeded / biased token id >= vocab
   kCkLogprobWant = 9,  // logprobs: a row's number of alternatives > 20
+  kCkPromptTarget = 10,  // prompt logprobs: a row's target id >= vocab
 };
 }  // namespace ft
 

@@ -19,6 +19,15 @@
 // distinct.  The global top-N is a subset of the union of the slices' top-N.  bf16
 // logits over 128k ids tie often; ties cost nothing here.  -0.0 orders as +0.0 (they
 // compare equal, so the id decides), as in a stable sort of the values.
+//
+// Prompt logprobs (ft_prompt_logprobs, SamplingParams.prompt_logprobs) are the same two
+// kernels instantiated with kRank: column 0 is a GIVEN id per row (the next prompt
+// token), and the row's rank = 1 + #{ids with a greater key} comes out as well.  K1 loads
+// the target's logit once per workgroup and counts, in the pass it makes anyway, its own
+// ids whose key exceeds the target's; K2 sums the 32 per-slice counts (integers: exact,
+// order-free, no atomics, no second read of the row).  Equal keys do not count, so ties
+// share a rank and -0.0 ranks as +0.0.  ft_logprobs launches the instantiations without
+// kRank: the code, workspace layout and results it always had.
 #include "ft_common.h"
 
 namespace ft {
@@ -33,6 +42,10 @@ constexpr int kLpMaxVocab = kLpSlices * kLpThreads * 8 * kLpChunks;
 // per-row scratch, 64-bit words: slice stats (M_p bits | Z_p bits << 32) x kLpSlices,
 // then kLpMax candidate words per slice (0 = none)
 constexpr int kLpWsCand = kLpSlices, kLpWsRow = kLpWsCand + kLpSlices * kLpMax;
+// prompt logprobs (ft_prompt_logprobs) count the target's rank as well: the same row
+// layout with one more word per slice behind it, the slice's number of ids whose key
+// exceeds the target's
+constexpr int kLpWsCount = kLpWsRow, kLpWsRowRank = kLpWsCount + kLpSlices;
 static_assert(kLpSlices <= 64 && kLpCols <= 64, "one lane per slice / output column");
 static_assert(kLpWaves * kLpMax <= 128, "two candidates per lane in the slice merge");
 
@@ -98,12 +111,22 @@ __device__ __forceinline__ int lp_want(const int* want, int row) {
   return min(FT_CHECK_IDX(w, kLpMax + 1, kCkLogprobWant, row), kLpMax);
 }
 
-template <typename T>
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// kRank (ft_prompt_logprobs): `targets` holds the row's given id; the slice also counts
+// its ids whose key exceeds the target's key, in the pass it makes anyway
+template <typename T, bool kRank>
 __global__ __launch_bounds__(kLpThreads) void logprob_slice_kernel(
     const T* __restrict__ logits, long stride, int vocab, const int* __restrict__ want,
-    lp_u64* __restrict__ ws) {
+    lp_u64* __restrict__ ws, const int* __restrict__ targets) {
+  constexpr int kWsRow = kRank ? kLpWsRowRank : kLpWsRow;
   __shared__ float s_m[kLpWaves], s_z[kLpWaves];
   __shared__ lp_u64 s_c[kLpWaves * kLpMax];
+  __shared__ int s_n[kRank ? kLpWaves : 1];
   const int row = blockIdx.y, p = blockIdx.x, tid = threadIdx.x, lane = lane_id();
   const int nk = lp_want(want, row);
   if (nk < 0) return;
@@ -126,6 +149,20 @@ __global__ __launch_bounds__(kLpThreads) void logprob_slice_kernel(
       key[8 * c + j] = j < n ? lp_key(v[j]) : 0u;
       m = fmaxf(m, f[8 * c + j]);
     }
+  }
+  if constexpr (kRank) {
+    // the target's logit, one (uniform) load per workgroup; an id outside the row is
+    // never read and counts nothing.  Keys of ids are never 0 and 0 marks "no id", so
+    // the comparison needs no validity test of its own.
+    const int t = targets[row];
+    int above = 0;
+    if (t >= 0 && t < vocab) {
+      const uint32_t tk = lp_key(lp_widen(x, t));
+#pragma unroll
+      for (int j = 0; j < 8 * kLpChunks; ++j) above += key[j] > tk ? 1 : 0;
+    }
+    above = wave_sum_i32(above);
+    if (lane == 0) s_n[wave_id()] = above;
   }
   m = wave_max(m);
   float z = 0.f;
@@ -168,7 +205,15 @@ __global__ __launch_bounds__(kLpThreads) void logprob_slice_kernel(
   if (wave_id() != 0) return;
 
   // wave 0: the slice's stats, and its nk best of the waves' candidates
-  lp_u64* wr = ws + (long)row * kLpWsRow;
+  lp_u64* wr = ws + (long)row * kWsRow;
+  if constexpr (kRank) {
+    if (lane == 0) {
+      int above = 0;
+#pragma unroll
+      for (int w = 0; w < kLpWaves; ++w) above += s_n[w];
+      wr[kLpWsCount + p] = (lp_u64)(uint32_t)above;
+    }
+  }
   if (lane == 0) {
     float M = s_m[0];
 #pragma unroll
@@ -194,17 +239,20 @@ __global__ __launch_bounds__(kLpThreads) void logprob_slice_kernel(
   if (lane < kLpMax) wr[kLpWsCand + p * kLpMax + lane] = mine;
 }
 
-template <typename T>
+// kRank: `sampled` holds the given target ids; the slices' counts are summed (integers:
+// exact, in any order) into out_rank = 1 + ids with a greater logit
+template <typename T, bool kRank>
 __global__ __launch_bounds__(64) void logprob_merge_kernel(
     const T* __restrict__ logits, long stride, int vocab, const int* __restrict__ sampled,
     const int* __restrict__ want, const lp_u64* __restrict__ ws, float* __restrict__ out_lp,
-    int* __restrict__ out_id) {
+    int* __restrict__ out_id, int* __restrict__ out_rank) {
+  constexpr int kWsRow = kRank ? kLpWsRowRank : kLpWsRow;
   constexpr int NC = kLpSlices * kLpMax / 64;   // candidate words per lane
   static_assert(NC * 64 == kLpSlices * kLpMax, "candidates divide over the wave");
   const int row = blockIdx.x, lane = threadIdx.x;
   const int nk = lp_want(want, row);
   if (nk < 0) return;
-  const lp_u64* wr = ws + (long)row * kLpWsRow;
+  const lp_u64* wr = ws + (long)row * kWsRow;
   float mp = -INFINITY, zp = 0.f;
   if (lane < kLpSlices) {
     const lp_u64 st = wr[lane];
@@ -237,15 +285,24 @@ __global__ __launch_bounds__(64) void logprob_merge_kernel(
       b = lane_best();
     }
   }
+  int above = 0;
+  if constexpr (kRank) above = wave_sum_i32(lane < kLpSlices ? (int)(uint32_t)wr[kLpWsCount + lane] : 0);
   if (lane >= kLpCols) return;
   int id = -1;
   float lp = 0.f;
   if (lane == 0) {
-    const int s = FT_CHECK_IDX(sampled[row], vocab, kCkSampled, row);
+    int s;
+    if constexpr (kRank) {
+      s = sampled[row];   // (the checked build records an id outside the row, and reads nothing)
+      (void)FT_CHECK_IDX(s, vocab, kCkPromptTarget, row);
+    } else {
+      s = FT_CHECK_IDX(sampled[row], vocab, kCkSampled, row);
+    }
     if (s >= 0 && s < vocab) {
       id = s;
       lp = logprob(lp_widen(logits + (long)row * stride, s));
     }
+    if constexpr (kRank) out_rank[row] = id >= 0 ? 1 + above : 0;
   } else if (mine != 0ull) {
     id = (int)~(uint32_t)mine;
     lp = logprob(lp_key_f32((uint32_t)(mine >> 32)));
@@ -272,13 +329,45 @@ extern "C" int ft_logprobs(const void* logits, int is_bf16, long stride, int row
 #define FT_LP_LAUNCH(TT)                                                                        \
   {                                                                                             \
     const TT* lg = static_cast<const TT*>(logits);                                              \
-    hipLaunchKernelGGL(logprob_slice_kernel<TT>, dim3(kLpSlices, rows), dim3(kLpThreads), 0,    \
-                       stream, lg, stride, vocab, want, w);                                     \
-    hipLaunchKernelGGL(logprob_merge_kernel<TT>, dim3(rows), dim3(64), 0, stream, lg, stride,   \
-                       vocab, sampled, want, (const lp_u64*)w, out_lp, out_id);                 \
+    hipLaunchKernelGGL((logprob_slice_kernel<TT, false>), dim3(kLpSlices, rows),                \
+                       dim3(kLpThreads), 0, stream, lg, stride, vocab, want, w,                 \
+                       (const int*)nullptr);                                                    \
+    hipLaunchKernelGGL((logprob_merge_kernel<TT, false>), dim3(rows), dim3(64), 0, stream, lg,  \
+                       stride, vocab, sampled, want, (const lp_u64*)w, out_lp, out_id,          \
+                       (int*)nullptr);                                                          \
   }
   if (is_bf16) FT_LP_LAUNCH(uint16_t) else FT_LP_LAUNCH(float)
 #undef FT_LP_LAUNCH
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int ft_prompt_logprobs_ws_words() { return ft::kLpWsRowRank; }
+
+// Prompt logprobs: as ft_logprobs with the given `targets` in place of the sampled ids,
+// plus out_rank [rows] = 1 + ids of the row with a greater logit (ties share a rank; 0 for
+// a target outside [0, vocab), which is never read).  ws: rows *
+// ft_prompt_logprobs_ws_words() 64-bit words.
+extern "C" int ft_prompt_logprobs(const void* logits, int is_bf16, long stride, int rows,
+                                  int vocab, const int* targets, const int* want, void* ws,
+                                  float* out_lp, int* out_id, int* out_rank,
+                                  hipStream_t stream) {
+  if (rows <= 0 || vocab <= 0) return 0;
+  if (rows > 65535) return -1;
+  if (vocab > ft::kLpMaxVocab) return -3;
+  if (stride % 8 != 0 || stride < vocab || reinterpret_cast<uintptr_t>(logits) % 16 != 0) return -4;
+  using namespace ft;
+  lp_u64* w = static_cast<lp_u64*>(ws);
+#define FT_PLP_LAUNCH(TT)                                                                       \
+  {                                                                                             \
+    const TT* lg = static_cast<const TT*>(logits);                                              \
+    hipLaunchKernelGGL((logprob_slice_kernel<TT, true>), dim3(kLpSlices, rows),                 \
+                       dim3(kLpThreads), 0, stream, lg, stride, vocab, want, w, targets);       \
+    hipLaunchKernelGGL((logprob_merge_kernel<TT, true>), dim3(rows), dim3(64), 0, stream, lg,   \
+                       stride, vocab, targets, want, (const lp_u64*)w, out_lp, out_id,          \
+                       out_rank);                                                               \
+  }
+  if (is_bf16) FT_PLP_LAUNCH(uint16_t) else FT_PLP_LAUNCH(float)
+#undef FT_PLP_LAUNCH
   return static_cast<int>(hipGetLastError());
 }
 

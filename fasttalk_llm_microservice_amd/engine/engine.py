@@ -144,6 +144,9 @@ class LLMEngine:
         # unfinished requests with SamplingParams.min_p > 0 (runner.mp_active: steps scan
         # their rows for it only while there is one)
         self._mp_reqs: set = set()
+        # unfinished requests with SamplingParams.prompt_logprobs (runner.plp_active:
+        # prefill chunks are scanned for unscored prompt positions only while there is one)
+        self._plp_reqs: set = set()
         # FT_PENALTY_VERIFY=1 (tests, debugging): a finishing sequence's slot is read back
         # and compared with the host's truth (_pen_verify)
         self.pen_verify = os.environ.get("FT_PENALTY_VERIFY", "0") == "1"
@@ -169,7 +172,12 @@ class LLMEngine:
             self._check_logprobs(params)
         if params.min_p > 0.0 and self.cfg.tp_size > 1:
             raise EngineError("min_p is not supported with tensor parallelism yet")
+        if params.prompt_logprobs is not None:
+            self._check_prompt_logprobs(params, background)
         seq = Sequence(request_id, prompt_ids, params, on_output, meta)
+        if params.prompt_logprobs is not None:
+            self._plp_reqs.add(request_id)
+            self.runner.plp_active = True
         if params.min_p > 0.0:
             self._mp_reqs.add(request_id)
             self.runner.mp_active = True
@@ -232,6 +240,44 @@ class LLMEngine:
             raise EngineError("logprobs are not supported with guided decoding")
         if not hasattr(self.runner, "take_logprobs"):
             raise EngineError("logprobs are not supported by this runner")
+
+    # ------------------------------------------------------------------ prompt logprobs
+    # A prefill chunk of a sequence that asked scores its prompt positions in the step
+    # that computes them (runner._plp_rows / _plp_launch); the step's handle carries
+    # (seq, epoch, first position, entries) per contributing chunk.  At collect a chunk
+    # whose sequence is unfinished and whose epoch still matches (its KV was not dropped
+    # after the chunk was queued) stores its entries in position order and advances
+    # plp_next; anything else is dropped, and no position is stored twice.  Until every
+    # position is scored the scheduler attaches cached prefix blocks only below plp_next.
+    def _check_prompt_logprobs(self, params: SamplingParams, background: bool):
+        if self.cfg.tp_size > 1:
+            raise EngineError("prompt_logprobs are not supported with tensor parallelism yet")
+        if params.guided is not None:
+            # jump-forward ids join the prompt: they have no given target
+            raise EngineError("prompt_logprobs are not supported with guided decoding")
+        if background:
+            raise EngineError("prompt_logprobs are not supported with background prefill")
+        if not hasattr(self.runner, "take_prompt_logprobs"):
+            raise EngineError("prompt_logprobs are not supported by this runner")
+
+    def _plp_store(self, chunks):
+        """``chunks``: runner.take_prompt_logprobs of a collected step (or None)."""
+        for seq, epoch, p0, entries in chunks or ():
+            if seq.plp is None or seq.status == SeqStatus.FINISHED or epoch != seq.epoch:
+                continue
+            for k, ent in enumerate(entries):
+                p = p0 + k
+                if p != seq.plp_next or p >= seq.prompt_len - 1:
+                    continue   # scored already (or out of order: left for a later chunk)
+                seq.plp[p + 1] = ent
+                seq.plp_next = p + 1
+
+    def _plp_first(self, seq: Sequence) -> Optional[list]:
+        """The sequence's prompt logprobs for its first output event; None on every other."""
+        if seq.plp is None or seq.plp_sent or seq.plp_next < seq.prompt_len - 1:
+            return None
+        seq.plp_sent = True
+        return seq.plp
 
     @staticmethod
     def _pen_wants(q: Sequence) -> bool:
@@ -588,12 +634,13 @@ class LLMEngine:
         tl = time.perf_counter()
         toks = self.runner.mixed_collect(handle) if e.mixed else self.runner.decode_collect(handle)
         lps = self.runner.take_logprobs(handle) if self._lp_reqs else None
+        plps = self.runner.take_prompt_logprobs(handle) if self._plp_reqs and e.mixed else None
         t1 = time.perf_counter()
         self._inflight.pop(0)
         sampled = batch.sampled_seqs()
         for q in sampled:
             q.inflight -= 1
-        outs = self._complete(batch, sampled, toks, lps)
+        outs = self._complete(batch, sampled, toks, lps, plps)
         # the guided step queued behind this one: its forward pass is running; its
         # sampler goes in now that this step's tokens have moved the grammars
         if self._inflight and getattr(self._inflight[0].handle, "pending", False):
@@ -622,9 +669,13 @@ class LLMEngine:
         hp["steps"] += 1
         return outs
 
-    def _complete(self, batch: ScheduledBatch, sampled_seqs, toks, lps=None) -> List[RequestOutput]:
-        """``lps``: the step's per-row logprob entries (runner.take_logprobs) or None."""
+    def _complete(self, batch: ScheduledBatch, sampled_seqs, toks, lps=None,
+                  plps=None) -> List[RequestOutput]:
+        """``lps``: the step's per-row logprob entries (runner.take_logprobs) or None;
+        ``plps``: its prompt-logprob chunks (runner.take_prompt_logprobs) or None."""
         outs: List[RequestOutput] = []
+        if plps is not None:
+            self._plp_store(plps)
         self.scheduler.post_step(batch)
         for i, (seq, tok) in enumerate(zip(sampled_seqs, toks)):
             if seq.drop_next:   # its forced tokens replaced this sample (jump-forward)
@@ -750,6 +801,8 @@ class LLMEngine:
         self._executing = batch
         toks = self.runner.execute(batch, masks)
         lps = self.runner.take_logprobs() if self._lp_reqs else None
+        if self._plp_reqs and batch.has_prefill:
+            self._plp_store(self.runner.take_prompt_logprobs())
         self._executing = None
         t1 = time.perf_counter()
         self.scheduler.post_step(batch)
@@ -827,6 +880,9 @@ class LLMEngine:
         p = seq.params
         if p.logprobs is not None and (lp is None or lp[0] != tok):
             raise EngineError(f"{seq.request_id}: the step returned no logprobs for token {tok}")
+        if seq.plp is not None and not seq.plp_sent and seq.plp_next < seq.prompt_len - 1:
+            raise EngineError(f"{seq.request_id}: {seq.plp_next} of {seq.prompt_len - 1} prompt "
+                              "logprobs were computed when the first token arrived")
         now = time.perf_counter()
         first = seq.first_token_time is None
         if first:
@@ -896,13 +952,14 @@ class LLMEngine:
             return self._finalize(seq, reason, emit=True, delta=delta, ids=ids, lps=lps)
         if not delta and not first:
             # nothing printable yet (partial UTF-8): still report progress
-            out = RequestOutput(seq.request_id, "", ids, num_output_tokens=n_out, logprobs=lps)
+            out = RequestOutput(seq.request_id, "", ids, num_output_tokens=n_out, logprobs=lps,
+                                prompt_logprobs=self._plp_first(seq))
         else:
             out = RequestOutput(seq.request_id, delta, ids, num_output_tokens=n_out,
                                 num_prompt_tokens=seq.prompt_len,
                                 num_cached_tokens=seq.num_cached_tokens,
                                 ttft_s=(seq.first_token_time - seq.arrival) if first else None,
-                                logprobs=lps)
+                                logprobs=lps, prompt_logprobs=self._plp_first(seq))
         if seq.on_output is not None:
             seq.on_output(out)
         return out
@@ -942,6 +999,9 @@ class LLMEngine:
         if self._mp_reqs:
             self._mp_reqs.discard(seq.request_id)
             self.runner.mp_active = bool(self._mp_reqs)
+        if self._plp_reqs:
+            self._plp_reqs.discard(seq.request_id)
+            self.runner.plp_active = bool(self._plp_reqs)
         if seq.pen_slot >= 0:
             try:
                 if self.pen_verify and reason != "error":
@@ -970,7 +1030,8 @@ class LLMEngine:
                             num_prompt_tokens=seq.prompt_len,
                             num_cached_tokens=seq.num_cached_tokens,
                             num_output_tokens=seq.num_output, error=error,
-                            logprobs=None if seq.params.logprobs is None else (lps or []))
+                            logprobs=None if seq.params.logprobs is None else (lps or []),
+                            prompt_logprobs=self._plp_first(seq))
         self.stats["finished_" + reason] += 1
         if emit and seq.on_output is not None:
             seq.on_output(out)
@@ -1055,6 +1116,8 @@ class LLMEngine:
             "penalty_steps": int(getattr(self.runner, "stats", {}).get("penalty_steps", 0)),
             "logprob_steps": int(getattr(self.runner, "stats", {}).get("logprob_steps", 0)),
             "logprob_rows": int(getattr(self.runner, "stats", {}).get("logprob_rows", 0)),
+            "prompt_logprob_steps": int(getattr(self.runner, "stats", {}).get("prompt_logprob_steps", 0)),
+            "prompt_logprob_rows": int(getattr(self.runner, "stats", {}).get("prompt_logprob_rows", 0)),
             "min_p_steps": int(getattr(self.runner, "stats", {}).get("min_p_steps", 0)),
             "swapped": len(self.scheduler.swapped),
             "swap_outs": self.scheduler.num_swap_out,

@@ -43,7 +43,7 @@ class KernelCheckError(RuntimeError):
              3: "position >= rotary table rows", 4: "input token id >= vocab",
              5: "sampled token id >= vocab", 6: "KV copy/swap block id >= num_blocks",
              7: "penalty slot >= max_num_seqs", 8: "penalty token id >= vocab",
-             9: "logprob alternatives > 20"}
+             9: "logprob alternatives > 20", 10: "prompt-logprob target id >= vocab"}
 
     def __init__(self, word):
         count, code, ctx, value = (int(x) for x in word[:4])
@@ -197,6 +197,54 @@ class _LpHost:
                 for r, w in enumerate(want)]
 
 
+class _PlpHost:
+    """Pinned host side of a step's prompt logprobs (SamplingParams.prompt_logprobs): the
+    three result arrays of ops.prompt_logprobs over the step's extra logits rows, and
+    which prompt positions they belong to.  ``chunks``: per contributing prefill chunk
+    ``(seq, epoch, first position, count, row offset)``; ``n``: rows held (0: none)."""
+    __slots__ = ("lp", "ids", "rank", "want", "chunks", "n", "pin")
+
+    def __init__(self, pin: bool):
+        self.pin = pin
+        self.n = 0
+        self.want: list = []
+        self.chunks: list = []
+        self._alloc(0)
+
+    def _alloc(self, rows: int):
+        cols = 1 + ops.LOGPROBS_MAX
+        self.lp = torch.zeros(rows, cols, dtype=torch.float32, pin_memory=self.pin and rows > 0)
+        self.ids = torch.zeros(rows, cols, dtype=torch.int32, pin_memory=self.pin and rows > 0)
+        self.rank = torch.zeros(rows, dtype=torch.int32, pin_memory=self.pin and rows > 0)
+
+    def stage(self, want: np.ndarray, chunks: list) -> int:
+        n = len(want)
+        if self.lp.shape[0] < n:
+            self._alloc(2 * n)
+        self.want, self.chunks, self.n = want.tolist(), chunks, n
+        return n
+
+    def take(self) -> Optional[list]:
+        """Per chunk ``(seq, epoch, first position, [(token_id, logprob, rank, [(alt_id,
+        alt_logprob), ...]), ...])``, or None when the step scored no prompt position.
+        Read after the step's event."""
+        n, self.n = self.n, 0
+        chunks, self.chunks = self.chunks, []
+        if not n:
+            return None
+        lp = self.lp.numpy()[:n].tolist()
+        ids = self.ids.numpy()[:n].tolist()
+        rank = self.rank.numpy()[:n].tolist()
+        out = []
+        for seq, epoch, p0, cnt, off in chunks:
+            ent = []
+            for r in range(off, off + cnt):
+                w = self.want[r]
+                ent.append((ids[r][0], lp[r][0], rank[r], list(zip(ids[r][1:1 + w], lp[r][1:1 + w]))))
+            out.append((seq, epoch, p0, ent))
+        return out
+
+
 class _Staging:
     """Pinned host mirror of the decode graph's device inputs + its output copy.
     int32 ``small`` fields: ids | pos | slots | seq_lens | top_k | steps."""
@@ -237,7 +285,8 @@ class MixedHandle:
     builds the step queued behind it once the GPU passes it).  They rotate; a
     handle is reused only after MIXED_HANDLES - 1 later mixed launches, more than
     the steps the engine keeps queued (ENGINE_PIPELINE_DEPTH + 1)."""
-    __slots__ = ("host", "event", "mark", "n", "pending", "logits", "samp", "seqs", "lp")
+    __slots__ = ("host", "event", "mark", "n", "pending", "logits", "samp", "seqs", "lp", "plp",
+                 "plp_job")
 
     def __init__(self, rows: int, pin: bool, gpu: bool):
         self.host = torch.zeros(rows, dtype=torch.int32, pin_memory=pin)
@@ -251,6 +300,10 @@ class MixedHandle:
         self.logits = None
         self.samp = None
         self.seqs = None   # deferred sampler: its rows (their penalty slots are read then)
+        # prompt logprobs of the step it holds (_PlpHost, made when a step first needs
+        # one); plp_job: what _plp_launch needs, kept until the step's sampler is queued
+        self.plp = None
+        self.plp_job = None
 
 
 MIXED_HANDLES = 4
@@ -427,6 +480,14 @@ class ModelRunner:
         self.d_lp = torch.zeros(mb, 1 + ops.LOGPROBS_MAX, dtype=torch.float32, device=dv)
         self.d_lp_ids = torch.zeros(mb, 1 + ops.LOGPROBS_MAX, dtype=i32, device=dv)
         self._lp_sync = _LpHost(mb, pin)
+        # prompt logprobs (ops.prompt_logprobs over extra logits rows of prefill chunks,
+        # _plp_launch): nothing is allocated until a request asks
+        self.plp_active = False   # the engine holds an unfinished request that asked
+        self.plp_slice_rows = 512   # LM-head rows per slice
+        self.plp_tap: Optional[list] = None   # tests: (request id, first position, raw logits)
+        self.d_plp = None
+        self._plp_sync: Optional[_PlpHost] = None
+        self._plp_last: Optional[_PlpHost] = None
         self._lp_last = self._lp_sync   # where the last synchronous step's results are
         # TP rank 0 decides about collective faults; workers only follow its messages
         self.checks_comm = comm.world_size > 1 and comm.rank == 0
@@ -511,6 +572,7 @@ class ModelRunner:
         self._trace_tp = os.environ.get("FT_TP_TRACE", "0") == "1" and comm.world_size > 1
         self.stats = {"graph_replays": 0, "eager_decode": 0, "prefill_steps": 0, "captures": 0,
                       "penalty_steps": 0, "logprob_steps": 0, "logprob_rows": 0,
+                      "prompt_logprob_steps": 0, "prompt_logprob_rows": 0,
                       "min_p_steps": 0}
         # tests: a list here collects every step's logits (fp32; eager steps on the host,
         # graph-replayed and mixed-ahead steps as stream-ordered device copies) -- TP-vs-TP=1
@@ -611,6 +673,7 @@ class ModelRunner:
         Decode-only steps replay a hipGraph; steps that carry prefill chunks run
         eagerly as one mixed forward pass (decode rows first)."""
         self._assert_no_pending_split("execute")
+        self._plp_last = None
         if batch.has_prefill:
             if self._gaps is not None:
                 self._gap_mark(True, "m")   # closed by _wait, right after the last launch
@@ -780,6 +843,85 @@ class ModelRunner:
         self.stats["logprob_steps"] += 1
         self.stats["logprob_rows"] += int((want >= 0).sum())
 
+    # ------------------------------------------------------------------ prompt logprobs
+    # A prefill chunk of a sequence that asked (SamplingParams.prompt_logprobs) names its
+    # not yet scored prompt positions as extra logits rows BEHIND the step's sampled rows
+    # (_mixed_host): the forward returns their hidden rows with the others, the sampler
+    # sees only the sampled ones.  The LM head runs over the extra rows in slices of at
+    # most plp_slice_rows (512 rows = 131 MB of bf16 logits at V = 128,256), each followed
+    # by ops.prompt_logprobs with the NEXT prompt token as the row's target, on the
+    # step's stream behind its sampler (behind the forward where it samples nothing).
+    # The results come back into the step's pinned _PlpHost before its event.  A step
+    # without such a row builds, uploads and launches exactly what it always did.
+    def _plp_rows(self, pseqs, ntoks, starts, qsl, nd: int):
+        """(rows, plp) of a step: the extra logits rows and ``{"targets", "want",
+        "chunks"}``, or ([], None) when no chunk of it has an unscored position."""
+        rows, tgt, want, chunks = [], [], [], []
+        for i, (s, n, a) in enumerate(zip(pseqs, ntoks, starts)):
+            if s.plp is None:
+                continue
+            if a is None:
+                a = s.num_computed
+            lo, hi = max(a, s.plp_next), min(a + n, s.prompt_len - 1)
+            if hi <= lo:
+                continue
+            chunks.append((s, s.epoch, lo, hi - lo, len(rows)))
+            base = nd + int(qsl[i]) - a
+            rows += list(range(base + lo, base + hi))
+            tgt.append(s.tokens[lo + 1:hi + 1])
+            want += [s.params.prompt_logprobs] * (hi - lo)
+        if not rows:
+            return [], None
+        return rows, {"targets": np.concatenate(tgt).astype(np.int32),
+                      "want": np.asarray(want, np.int32), "chunks": chunks}
+
+    @staticmethod
+    def _plp_split(h, host, d_lrows):
+        """(sampled rows, extra rows) of the forward's hidden rows ``h``.  The forward
+        returns ALL rows in their natural order when as many rows are named as the step
+        has tokens (it takes that for "every row"): with extra rows the names are then a
+        permutation of the rows, which is applied here."""
+        n = len(host["lrows"])
+        if n == len(host["ids"]):
+            h = h.index_select(0, d_lrows)
+        ns = n - len(host["plp"]["want"])   # the sampled rows come first
+        return h[:ns], h[ns:]
+
+    def _plp_launch(self, hb: "_PlpHost", hidden, plp, d_tgt, d_want):
+        """Queues a step's prompt logprobs: the LM head over ``hidden`` (the extra rows)
+        slice by slice, ops.prompt_logprobs behind each, the results down into ``hb``."""
+        n = hb.stage(plp["want"], plp["chunks"])
+        if self.d_plp is None or self.d_plp[0].shape[0] < n:
+            dv, cols = self.device, 1 + ops.LOGPROBS_MAX
+            self.d_plp = (torch.zeros(2 * n, cols, dtype=torch.float32, device=dv),
+                          torch.zeros(2 * n, cols, dtype=torch.int32, device=dv),
+                          torch.zeros(2 * n, dtype=torch.int32, device=dv))
+        dl, di, dr = (t[:n] for t in self.d_plp)
+        step = max(1, int(self.plp_slice_rows))
+        taps = [] if self.plp_tap is not None else None
+        for o in range(0, n, step):
+            m = min(step, n - o)
+            logits = self.model.compute_logits(hidden[o:o + m])
+            if taps is not None:
+                taps.append(logits.float().cpu())
+            ops.prompt_logprobs(logits, d_tgt[o:o + m], d_want[o:o + m], dl[o:o + m], di[o:o + m],
+                                dr[o:o + m])
+        hb.lp[:n].copy_(dl, non_blocking=True)
+        hb.ids[:n].copy_(di, non_blocking=True)
+        hb.rank[:n].copy_(dr, non_blocking=True)
+        if taps is not None:
+            raw = torch.cat(taps)
+            for seq, _, p0, cnt, off in plp["chunks"]:
+                self.plp_tap.append((seq.request_id, p0, raw[off:off + cnt]))
+        self.stats["prompt_logprob_steps"] += 1
+        self.stats["prompt_logprob_rows"] += n
+
+    def take_prompt_logprobs(self, h=None) -> Optional[list]:
+        """The prompt-logprob chunks of a collected step (``h``: its handle; None: the
+        synchronous step ``execute`` just ran), or None when it scored no position."""
+        hb = self._plp_last if h is None else getattr(h, "plp", None)
+        return hb.take() if hb is not None else None
+
     def take_logprobs(self, h=None) -> Optional[list]:
         """The per-row logprob entries of a collected step (``h``: its handle; None: the
         synchronous step ``execute`` just ran), or None when no row of it asked."""
@@ -847,6 +989,10 @@ class ModelRunner:
             fixed_chunk=ops.PREFILL_INV_CHUNK if self.invariant else 0)
         # logits rows: every decode row + the last row of each prompt that completes
         lrows = list(range(nd)) + [nd + int(qsl[i + 1]) - 1 for i, sm in enumerate(psamp) if sm]
+        host["plp"] = None
+        if self.plp_active:   # prompt-logprob rows go behind the sampled rows
+            xrows, host["plp"] = self._plp_rows(pseqs, ntoks, starts, qsl, nd)
+            lrows += xrows
         host.update(ids=np.concatenate(ids).astype(np.int32), pos=np.concatenate(pos).astype(np.int32),
                     slots=np.concatenate(slots).astype(np.int32), lrows=np.asarray(lrows, np.int64),
                     bt=bt, seq_lens=seq_lens, qsl=qsl, tiles=np.asarray(tiles, np.int32).reshape(-1),
@@ -887,8 +1033,14 @@ class ModelRunner:
             if nd > self.max_decode_rows:
                 raise ValueError(f"{nd} decode rows exceed max_num_seqs {self.max_decode_rows}")
             names += ["d_bt", "d_sl"]
+        plp = host.get("plp")
+        if plp is not None:
+            names += ["plp_t", "plp_w"]
+            host["plp_t"], host["plp_w"] = plp["targets"], plp["want"]
         arrays = [host[k] for k in names]
-        has_logits = len(host["lrows"]) > 0
+        ns = len(host["lrows"]) - (len(plp["want"]) if plp is not None else 0)   # sampled rows
+        has_logits = ns > 0
+        self._plp_last = None
         pen = host.get("pen") if has_logits else None
         minp = host.get("minp") if has_logits else None
         if has_logits:
@@ -919,7 +1071,16 @@ class ModelRunner:
             meta.tmp_out, meta.tmp_ml = self.tmp_out, self.tmp_ml
             meta.dec_counters = self.dec_counters
         h = self.model.forward(d["ids"], meta, self.kv)
+        job = None
+        if plp is not None:
+            if self._plp_sync is None:
+                self._plp_sync = _PlpHost(self.is_gpu)
+            h, hx = self._plp_split(h, host, d["lrows"])
+            job = (self._plp_sync, hx, plp, d["plp_t"], d["plp_w"])
+            self._plp_last = self._plp_sync
         if not has_logits:
+            if job is not None:   # a chunk that samples nothing still scores its positions
+                self._plp_launch(*job)
             # a middle chunk of a chunked prefill samples nothing, but its all-reduces
             # wrote KV blocks that post_step commits to the prefix cache: check the
             # custom collectives' error word before anything is committed
@@ -929,6 +1090,8 @@ class ModelRunner:
                 self._wait()
                 if int(self.h_err[0]):
                     self._comm_fault()
+            elif job is not None and self.is_gpu:
+                self._wait()
             return []
         k = len(names)
         samp = list(dev[k:k + 5])
@@ -937,7 +1100,7 @@ class ModelRunner:
             samp.append(dev[k + 5 + (masks is not None)])
         dpen = dev[-4:] if pen is not None else None
         return self._sample(h, host["sampling"], masks, dev_sampling=samp, dev_mask=dmask,
-                            dev_pen=dpen, lp_want=host.get("lp"))
+                            dev_pen=dpen, lp_want=host.get("lp"), plp_job=job)
 
     def _wait(self, ev=None):
         """Block until the GPU work queued so far (or up to ``ev``) is done WITHOUT
@@ -997,7 +1160,7 @@ class ModelRunner:
             self.d_check.zero_()
 
     def _sample(self, h, sampling, masks, dev_sampling=None, dev_mask=None, dev_pen=None,
-                lp_want=None) -> List[int]:
+                lp_want=None, plp_job=None) -> List[int]:
         logits = self.model.compute_logits(h)
         self._lp_sync.n = 0
         self._lp_last = self._lp_sync
@@ -1014,6 +1177,8 @@ class ModelRunner:
         out = self._pen_sample(logits, dev_sampling, dev_mask, dev_pen)
         if lp_want is not None:
             self._lp_launch(self._lp_sync, lp_want, logits, out)
+        if plp_job is not None:
+            self._plp_launch(*plp_job)
         if not self.is_gpu:
             return out.tolist()
         n = out.shape[0]
@@ -1268,6 +1433,10 @@ class ModelRunner:
         names = ["pos", "slots", "lrows", "bt", "seq_lens", "qsl", "tiles", "ids", "combine"]
         if nd:
             names += ["d_bt", "d_sl"]
+        plp = host["plp"]
+        if plp is not None:
+            names += ["plp_t", "plp_w"]
+            host["plp_t"], host["plp_w"] = plp["targets"], plp["want"]
         arrays = [host[k] for k in names] + list(host["sampling"])
         minp = host["minp"]
         # rowmap[i] < 0: row i's sequence has no queued step (it joined after the last
@@ -1315,6 +1484,7 @@ class ModelRunner:
             meta.dec_counters = self.dec_counters
         mh = self._mx_handles[self._mx_next]
         self._mx_next = (self._mx_next + 1) % len(self._mx_handles)
+        mh.plp_job = None   # (left by a deferred step whose sampler was never queued)
         nl = len(getattr(self.model, "layers", ()))
         if mh.mark is not None and nl and self.mixed_mark_frac > 0:
             self.model.mark_at = (min(nl - 1, int(self.mixed_mark_frac * nl)), mh.mark)
@@ -1322,6 +1492,14 @@ class ModelRunner:
             h = self.model.forward(d["ids"], meta, self.kv)
         finally:
             self.model.mark_at = None
+        if plp is not None:
+            h, hx = self._plp_split(h, host, d["lrows"])
+            if mh.plp is None:
+                mh.plp = _PlpHost(self.is_gpu)
+            dt, dw = d["plp_t"], d["plp_w"]
+            if defer_sample:   # (views of the upload buffer, as the sampling arrays below)
+                dt, dw = dt.clone(), dw.clone()
+            mh.plp_job = (mh.plp, hx, plp, dt, dw)
         logits = self.model.compute_logits(h)
         if self.logits_tap is not None:
             self._tap(logits.float().cpu())   # taps are host tensors (tests)
@@ -1359,6 +1537,11 @@ class ModelRunner:
         mh.lp.n = 0
         if lp_want is not None:
             self._lp_launch(mh.lp, lp_want, logits, self.d_out)
+        if mh.plp is not None:
+            mh.plp.n, mh.plp.chunks = 0, []
+        if mh.plp_job is not None:
+            job, mh.plp_job = mh.plp_job, None
+            self._plp_launch(*job)
         mh.host[:mh.n].copy_(self.d_out[:mh.n], non_blocking=self.is_gpu)
         if mh.event is not None:
             mh.event.record()

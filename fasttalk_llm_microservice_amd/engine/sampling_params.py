@@ -47,6 +47,20 @@ def pick_logprobs(src) -> Optional[int]:
     return top
 
 
+def pick_prompt_logprobs(src) -> Optional[int]:
+    """vLLM's ``prompt_logprobs: n`` of a request body as SamplingParams.prompt_logprobs:
+    None when the request does not ask, else n.  A non-integer or an n outside 0..20
+    raises ValueError."""
+    v = src.get("prompt_logprobs")
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError("prompt_logprobs must be an integer")
+    if not 0 <= v <= LOGPROBS_MAX:
+        raise ValueError(f"prompt_logprobs must be in 0..{LOGPROBS_MAX}")
+    return v
+
+
 def pick_min_p(src) -> dict:
     """``min_p`` of a request dict (an OpenAI body, a WebSocket session config) as
     SamplingParams keywords: empty when the request does not set it.  Validated: raises
@@ -100,6 +114,10 @@ class SamplingParams:
     # allow-mask and temperature, before top-k / top-p, a token is kept iff
     # p(token) >= min_p * p_max (ops/reference.py sample).  Greedy rows ignore it.
     min_p: float = 0.0
+    # vLLM ``prompt_logprobs``: None = off, 0..20 = for every prompt position after the
+    # first, the prompt token's logprob and rank given the tokens before it, plus that
+    # many most likely alternatives -- over the raw logits, like ``logprobs``
+    prompt_logprobs: Optional[int] = None
 
     MAX_LOGIT_BIAS = 300
 
@@ -117,6 +135,13 @@ class SamplingParams:
             return
         if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= LOGPROBS_MAX:
             raise ValueError(f"logprobs must be None or an integer in 0..{LOGPROBS_MAX}")
+
+    def _check_prompt_logprobs(self):
+        v = self.prompt_logprobs
+        if v is None:
+            return
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= LOGPROBS_MAX:
+            raise ValueError(f"prompt_logprobs must be None or an integer in 0..{LOGPROBS_MAX}")
 
     @property
     def has_penalties(self) -> bool:
@@ -160,6 +185,7 @@ class SamplingParams:
     def __post_init__(self):
         self._check_penalties()
         self._check_logprobs()
+        self._check_prompt_logprobs()
         self._check_min_p()
         if self.temperature is None:
             self.temperature = 0.7

@@ -302,6 +302,17 @@ class Scheduler:
         seq.pf_sched = 0
         seq.epoch += 1
 
+    def _prefix_blocks(self, seq: Sequence) -> int:
+        """Most cached blocks an admission of ``seq`` may attach.  A sequence that asked
+        for prompt logprobs needs the logits of every prompt position: until all are
+        scored (``plp_next == prompt_len - 1``) only blocks below ``plp_next`` may come
+        from the cache -- none on a first admission, what has been scored on a recompute
+        after preemption."""
+        n = (seq.n_tokens - 1) // self.bs
+        if seq.plp is not None and seq.plp_next < seq.prompt_len - 1:
+            n = min(n, seq.plp_next // self.bs)
+        return n
+
     def _schedule_prefill(self, budget: int, n_decode: int, reserved: int = 0):
         """``reserved``: sequences that count against ``max_num_seqs`` without being decode
         rows of this step -- prompts completed by a queued mixed step that have not joined
@@ -327,7 +338,7 @@ class Scheduler:
                 break
             seq = self.waiting[0]
             if seq.num_computed == 0 and not seq.block_ids:
-                max_blocks = (seq.n_tokens - 1) // self.bs
+                max_blocks = self._prefix_blocks(seq)
                 if max_blocks > 0:
                     hit = self.bm.match_prefix(seq.tokens, max_blocks)
                     if hit:
@@ -404,7 +415,7 @@ class Scheduler:
         Warm-up is optional work: under KV pressure it is dropped, not waited for."""
         seq = self.background[0]
         if seq.num_computed == 0 and not seq.block_ids:
-            max_blocks = (seq.n_tokens - 1) // self.bs
+            max_blocks = self._prefix_blocks(seq)
             hit = self.bm.match_prefix(seq.tokens, max_blocks) if max_blocks > 0 else []
             if hit:
                 seq.block_ids = list(hit)

@@ -34,6 +34,10 @@ class RequestOutput:
     # SamplingParams.logprobs: one (token_id, logprob, [(alt_id, alt_logprob), ...]) per
     # entry of token_ids; None when the request did not ask
     logprobs: Optional[list] = None
+    # SamplingParams.prompt_logprobs: on the request's FIRST event, one entry per prompt
+    # token -- None for the first, then (token_id, logprob, rank, [(alt_id, alt_logprob),
+    # ...]); None on every other event and when the request did not ask
+    prompt_logprobs: Optional[list] = None
 
 
 class Sequence:
@@ -42,7 +46,8 @@ class Sequence:
                  "first_token_time", "finish_reason", "detok_stream", "on_output", "grammar",
                  "grammar_state", "stop_buf", "text_len", "aborted", "preemptions", "admit_order",
                  "meta", "host_slots", "background", "jf_text", "jf_ids", "lazy", "inflight",
-                 "drop_next", "pf_sched", "epoch", "pen_slot")
+                 "drop_next", "pf_sched", "epoch", "pen_slot", "plp", "plp_next",
+                 "plp_sent")
 
     def __init__(self, request_id: str, prompt_ids: List[int], params: SamplingParams,
                  on_output: Optional[Callable[[RequestOutput], None]] = None, meta: Any = None):
@@ -93,6 +98,15 @@ class Sequence:
         # penalties: the sequence's slot of the runner's device state (engine free list);
         # -1 = none (no penalties, not scheduled yet, preempted, or its grammar is bound)
         self.pen_slot = -1
+        # SamplingParams.prompt_logprobs: one entry per prompt token (entry 0 stays None;
+        # entry j = (token_id, logprob, rank, alternatives) of prompt token j given the
+        # tokens before it), filled in position order as prefill chunks are collected;
+        # plp_next = prompt positions whose logits have been scored so far (entry p + 1
+        # comes from position p).  Until plp_next reaches prompt_len - 1 the prefix cache
+        # may only re-attach blocks below it (scheduler).  plp None: not asked.
+        self.plp: Optional[list] = None if params.prompt_logprobs is None else [None] * self.prompt_len
+        self.plp_next = 0
+        self.plp_sent = False
 
     # ---------------------------------------------------------------- tokens
     @property
@@ -133,6 +147,7 @@ def coalesce(first: RequestOutput, q) -> RequestOutput:
     text = [first.text]
     ids = list(first.token_ids)
     lps = None if first.logprobs is None else list(first.logprobs)
+    plp = first.prompt_logprobs
     o = first
     while not q.empty() and not o.finished:
         o = q.get_nowait()
@@ -140,7 +155,10 @@ def coalesce(first: RequestOutput, q) -> RequestOutput:
         ids.extend(o.token_ids)
         if lps is not None and o.logprobs is not None:
             lps.extend(o.logprobs)
+        if plp is None:
+            plp = o.prompt_logprobs
     return RequestOutput(first.request_id, "".join(text), ids, finished=o.finished, logprobs=lps,
+                         prompt_logprobs=plp,
                          finish_reason=o.finish_reason,
                          num_prompt_tokens=first.num_prompt_tokens or o.num_prompt_tokens,
                          num_cached_tokens=first.num_cached_tokens or o.num_cached_tokens,

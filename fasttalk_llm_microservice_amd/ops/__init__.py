@@ -481,6 +481,25 @@ def logprobs(logits, sampled, want, out_lp=None, out_id=None):
     return out_lp, out_id
 
 
+def prompt_logprobs(logits, targets, want, out_lp=None, out_id=None, out_rank=None):
+    """``(out_lp, out_id, out_rank)`` of given ids: :func:`logprobs` with ``targets[r]`` in
+    place of the sampled id (column 0), plus ``out_rank`` int32 [B] = 1 + the ids of the
+    row whose logit (widened to fp32, -0.0 == +0.0) is greater than the target's -- ties
+    share a rank.  A target outside [0, V) is never read: id -1, logprob 0.0, rank 0.  Rows
+    with ``want[r] == -1`` are left untouched (reference.prompt_logprobs)."""
+    if not logits.is_cuda:
+        return ref.prompt_logprobs(logits, targets, want, out_lp, out_id, out_rank)
+    b = logits.shape[0]
+    if out_lp is None:
+        out_lp = torch.zeros(b, 1 + LOGPROBS_MAX, dtype=torch.float32, device=logits.device)
+    if out_id is None:
+        out_id = torch.full((b, 1 + LOGPROBS_MAX), -1, dtype=torch.int32, device=logits.device)
+    if out_rank is None:
+        out_rank = torch.zeros(b, dtype=torch.int32, device=logits.device)
+    native().prompt_logprobs(logits, targets, want, out_lp, out_id, out_rank)
+    return out_lp, out_id, out_rank
+
+
 def kv_block_copy(k_cache, v_cache, pairs: torch.Tensor):
     if k_cache.is_cuda:
         native().kv_block_copy(k_cache, v_cache, pairs)

@@ -264,6 +264,43 @@ def token_logprobs(logits: torch.Tensor, sampled, want, out_lp: Optional[torch.T
     return out_lp, out_id
 
 
+def prompt_logprobs(logits: torch.Tensor, targets, want, out_lp: Optional[torch.Tensor] = None,
+                    out_id: Optional[torch.Tensor] = None,
+                    out_rank: Optional[torch.Tensor] = None):
+    """Prompt logprobs (SamplingParams.prompt_logprobs), the reference of
+    csrc/kernels/logprobs.hip ft_prompt_logprobs and the CPU backend:
+    ``(out_lp fp32 [B, 1 + 20], out_id int32 [B, 1 + 20], out_rank int32 [B])``.
+
+    As :func:`token_logprobs` with the GIVEN id ``targets[r]`` in column 0, plus
+    ``out_rank[r] = 1 + #{ids whose logit is greater than the target's}``: compared on the
+    logits widened to fp32, -0.0 equal to +0.0, ties sharing a rank.  A -inf target has
+    logprob -inf and the rank that definition gives (1 + the finite ids).  A target
+    outside [0, V) reads nothing: id -1, logprob 0.0, rank 0.  Rows with ``want[r] == -1``
+    are left as they are (new outputs: id -1, logprob 0.0, rank 0)."""
+    x = logits.float()
+    b, v = x.shape
+    dev = x.device
+    if out_rank is None:
+        out_rank = torch.zeros(b, dtype=torch.int32, device=dev)
+    want_t = torch.as_tensor(want, dtype=torch.int64, device=dev).reshape(-1)[:b]
+    tgt = torch.as_tensor(targets, dtype=torch.int64, device=dev).reshape(-1)[:b]
+    ok = (tgt >= 0) & (tgt < v)
+    out_lp, out_id = token_logprobs(x, torch.where(ok, tgt, torch.zeros_like(tgt)), want_t,
+                                    out_lp, out_id)
+    rows = torch.nonzero(want_t >= 0).flatten()
+    if not rows.numel():
+        return out_lp, out_id, out_rank
+    okr = ok[rows]
+    tv = x[rows].gather(1, tgt[rows].clamp(0, v - 1).view(-1, 1))
+    rank = 1 + (x[rows] > tv).sum(dim=-1)
+    out_rank[rows] = torch.where(okr, rank, torch.zeros_like(rank)).to(torch.int32)
+    bad = rows[~okr]
+    if bad.numel():
+        out_lp[bad, 0] = 0.0
+        out_id[bad, 0] = -1
+    return out_lp, out_id, out_rank
+
+
 def sample(logits: torch.Tensor, temperature, top_p, top_k, seeds, steps,
            mask: Optional[torch.Tensor] = None,
            min_p: Optional[torch.Tensor] = None) -> torch.Tensor:
