@@ -104,6 +104,12 @@ int ft_packed_gemm(const void* x, int x_stride, int M, const void* wpk, int N, i
 int ft_w4_packed_gemm(const void* x, int x_stride, int M, const uint32_t* wq, const void* sz, int N,
                       int K, int splits, int epi, int cfg, void* out, int out_stride, float* ws,
                       hipStream_t stream);
+int ft_w8_gemm(const void* x, int x_stride, int M, const uint8_t* wq, const float* scale, int N,
+               int K, float* ws, long ws_floats, void* out, int out_stride, int splits, int nt,
+               int silu, hipStream_t stream);
+int ft_w8_packed_gemm(const void* x, int x_stride, int M, const uint8_t* wq, const float* scale,
+                      int N, int K, int splits, int epi, int cfg, void* out, int out_stride,
+                      float* ws, long ws_floats, hipStream_t stream);
 int ft_pkr_gemm(const void* x, int x_stride, int M, const void* wpk, int N, int K, float* ws,
                 void* out, int out_stride, void* residual, int res_stride, int* tickets,
                 int splits, int nt, int depth, int epi, int norm, int wn, float eps,
@@ -713,6 +719,87 @@ void w4_packed_gemm(at::Tensor x, at::Tensor wq, at::Tensor sz, int64_t N,
            "w4_packed_gemm");
 }
 
+// W8A16: wq uint8 fp8 image [N/16][K/64][64][16], scale fp32 [N] (image row order); see
+// w8a16.hip.  The tensors are checked here; every argument the kernels constrain (row
+// count, divisibility, split / epilogue combinations, workspace size) is checked by the
+// launchers before any launch, and the *_rc forms return their code to the caller.
+void check_w8(const at::Tensor& wq, const at::Tensor& scale, int64_t N, int64_t K) {
+  check_dev(wq, "wq");
+  check_dev(scale, "scale");
+  TORCH_CHECK(wq.scalar_type() == at::kByte && wq.is_contiguous(), "wq uint8 contiguous");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous(), "scale fp32 contiguous");
+  TORCH_CHECK(N > 0 && K > 0 && wq.numel() == N * K, "wq size");
+  TORCH_CHECK(scale.numel() == N, "scale size");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0, "wq must be 16-B aligned");
+}
+
+// out / ws of a W8 call -> raw pointers; out must hold [M, cols]
+void w8_outputs(const c10::optional<at::Tensor>& out, const c10::optional<at::Tensor>& ws, int M,
+                int64_t cols, void** op, int* ostride, float** wsp, long* ws_floats) {
+  if (ws.has_value()) {
+    check_dev(*ws, "workspace");
+    TORCH_CHECK(ws->scalar_type() == at::kFloat && ws->is_contiguous(), "workspace fp32 contiguous");
+    *wsp = ws->data_ptr<float>();
+    *ws_floats = (long)ws->numel();
+  }
+  if (out.has_value()) {
+    check_bf16(*out, "out");
+    TORCH_CHECK(out->dim() == 2 && out->stride(1) == 1 && out->size(0) >= M && out->size(1) >= cols,
+                "out shape");
+    *op = out->data_ptr();
+    *ostride = (int)out->stride(0);
+  }
+}
+
+// y = scale * (x q^T) for M <= 64 rows (w8a16.hip); with ws: fp32 slabs [splits, M, N]
+int64_t w8_gemm_rc(at::Tensor x, at::Tensor wq, at::Tensor scale, int64_t N,
+                   c10::optional<at::Tensor> out, c10::optional<at::Tensor> ws, int64_t splits,
+                   int64_t nt, bool silu) {
+  check_bf16(x, "x");
+  check_rows(x, "x");
+  const int M = (int)x.size(0), K = (int)x.size(1);
+  check_w8(wq, scale, N, K);
+  float* wsp = nullptr;
+  long ws_floats = 0;
+  void* op = nullptr;
+  int ostride = 0;
+  w8_outputs(out, ws, M, silu ? N / 2 : N, &op, &ostride, &wsp, &ws_floats);
+  return ft_w8_gemm(x.data_ptr(), (int)x.stride(0), M, wq.data_ptr<uint8_t>(),
+                    scale.data_ptr<float>(), (int)N, K, wsp, ws_floats, ws.has_value() ? nullptr : op,
+                    ostride, (int)splits, (int)nt, silu ? 1 : 0, cur_stream());
+}
+
+void w8_gemm(at::Tensor x, at::Tensor wq, at::Tensor scale, int64_t N, c10::optional<at::Tensor> out,
+             c10::optional<at::Tensor> ws, int64_t splits, int64_t nt, bool silu) {
+  check_rc((int)w8_gemm_rc(x, wq, scale, N, out, ws, splits, nt, silu), "w8_gemm");
+}
+
+// W8A16 GEMM for any row count on the fp8 image (w8_packed_gemm.hip).  epi: 0 bf16 out
+// [M, N] (one split), 1 fp32 slabs ws [splits, M, N], 2 SiLU-mul out [M, N/2].
+int64_t w8_packed_gemm_rc(at::Tensor x, at::Tensor wq, at::Tensor scale, int64_t N,
+                          c10::optional<at::Tensor> out, c10::optional<at::Tensor> ws,
+                          int64_t splits, int64_t epi, int64_t cfg) {
+  check_bf16(x, "x");
+  check_rows(x, "x");
+  const int M = (int)x.size(0), K = (int)x.size(1);
+  check_w8(wq, scale, N, K);
+  float* wsp = nullptr;
+  long ws_floats = 0;
+  void* op = nullptr;
+  int ostride = 0;
+  w8_outputs(out, ws, M, epi == 2 ? N / 2 : N, &op, &ostride, &wsp, &ws_floats);
+  return ft_w8_packed_gemm(x.data_ptr(), (int)x.stride(0), M, wq.data_ptr<uint8_t>(),
+                           scale.data_ptr<float>(), (int)N, K, (int)splits, (int)epi, (int)cfg,
+                           epi == 1 ? nullptr : op, ostride, epi == 1 ? wsp : nullptr, ws_floats,
+                           cur_stream());
+}
+
+void w8_packed_gemm(at::Tensor x, at::Tensor wq, at::Tensor scale, int64_t N,
+                    c10::optional<at::Tensor> out, c10::optional<at::Tensor> ws, int64_t splits,
+                    int64_t epi, int64_t cfg) {
+  check_rc((int)w8_packed_gemm_rc(x, wq, scale, N, out, ws, splits, epi, cfg), "w8_packed_gemm");
+}
+
 void w4_dequant(at::Tensor wq, at::Tensor sz, at::Tensor out) {
   check_bf16(out, "out");
   TORCH_CHECK(out.dim() == 2 && out.is_contiguous(), "out [N, K] contiguous");
@@ -1208,6 +1295,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nt") = 1, py::arg("xr") = false, py::arg("silu") = false);
   m.def("w4_dequant", &w4_dequant);
   m.def("w4_packed_gemm", &w4_packed_gemm);
+  m.def("w8_gemm", &w8_gemm);
+  m.def("w8_gemm_rc", &w8_gemm_rc);
+  m.def("w8_packed_gemm", &w8_packed_gemm);
+  m.def("w8_packed_gemm_rc", &w8_packed_gemm_rc);
   m.def("skinny_gemm_xr", &skinny_gemm_xr, py::arg("x"), py::arg("w"), py::arg("out") = py::none(),
         py::arg("ws") = py::none(), py::arg("splits") = 1, py::arg("nt") = 2, py::arg("epi") = 0,
         py::arg("nw") = 4);

@@ -66,7 +66,9 @@ class EngineConfig:
     custom_allreduce: bool = True
     tp_share_device: bool = False      # TP ranks all on device_base (tests: gloo control + IPC data)
     max_restarts: int = 3              # separate-process engines: respawns after a replica dies
-    quantization: Optional[str] = None  # None | "awq" | "w4" (W4A16, group 128; --quantization awq)
+    # None | "awq" | "w4" (W4A16, group 128; --quantization awq) | "fp8" (W8A16: e4m3
+    # weights with per-channel scales, --quantization fp8; tp_size 1, not batch-invariant)
+    quantization: Optional[str] = None
     # a sequence's tokens independent of what else shares its steps (fixed GEMM splits,
     # fixed-piece attention partitions; TP=1, bf16; slower decode attention)
     batch_invariant: bool = False
@@ -94,6 +96,19 @@ class EngineConfig:
             self.penalties = _bool(os.environ.get("ENGINE_PENALTIES", "1") or "1")
         self.check_kv_scales()
         self.check_w4_prefill()
+        self.check_quantization()
+
+    def check_quantization(self) -> Optional[str]:
+        """What fp8 weights cannot be combined with yet; ValueError for those."""
+        q = (self.quantization or "").strip().lower() or None
+        if q == "fp8":
+            if self.tp_size > 1:
+                raise ValueError("quantization='fp8' does not support tensor parallelism yet "
+                                 f"(tp_size={self.tp_size})")
+            if self.batch_invariant:
+                raise ValueError("quantization='fp8' does not support batch-invariant mode yet "
+                                 "(ENGINE_BATCH_INVARIANT=1)")
+        return q
 
     def check_w4_prefill(self) -> str:
         """auto | image | scratch | int4 (normalised in place); ValueError otherwise."""
@@ -191,6 +206,7 @@ class EngineConfig:
             setattr(c, k, v)
         c.check_kv_scales()
         c.check_w4_prefill()
+        c.check_quantization()
         if c.separate_process is None:
             # a TP group runs in its own process by default: when a worker dies the
             # supervisor (parallel/dp_router.py) can tear the group down and respawn it

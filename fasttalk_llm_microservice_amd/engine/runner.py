@@ -355,9 +355,13 @@ class ModelRunner:
         w4_mode = self.model.w4_prefill_mode()
         if w4_mode is not None:
             self.weights_info["w4_prefill"] = w4_mode
-        log.info("weights ready in %.1fs: %.3f GB resident%s", time.time() - t0,
+        if self.model.quant == "fp8":   # only then: every other engine reports what it did
+            self.weights_info["quantization"] = "fp8"
+        log.info("weights ready in %.1fs: %.3f GB resident%s%s", time.time() - t0,
                  self.weights_info["weights_resident_gb"],
-                 f", W4 above 64 rows: {w4_mode}" if w4_mode else "")
+                 f", W4 above 64 rows: {w4_mode}" if w4_mode else "",
+                 ", quantization fp8 (e4m3 weights, per-channel scales; bench.py still labels "
+                 "the dtype bf16)" if self.model.quant == "fp8" else "")
 
         # batch-invariant numerics (cfg.batch_invariant): rows of a step up to the token
         # budget plus a decode row per sequence

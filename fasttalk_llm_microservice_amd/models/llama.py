@@ -87,6 +87,9 @@ class LayerWeights:
     fd: Optional[torch.Tensor] = None
     # W4A16 (AWQ) projections by name ("qkv", "o", "gu", "down"), GPU only
     q4: Optional[dict] = None
+    # W8A16 (fp8 e4m3, per-channel scales) projections by name, GPU only: the fp8 image
+    # is the only resident copy of a projection
+    q8: Optional[dict] = None
 
 
 _ATTR = {"qkv": "wqkv", "o": "wo", "gu": "wgu", "down": "wd"}
@@ -398,6 +401,59 @@ def w4_fits(xr: int, nt: int, sp: int, n: int, k: int) -> bool:
     return n % (16 * nt) == 0 and k % (128 * sp) == 0
 
 
+# W8A16 (fp8 e4m3 weights, per-channel scales; csrc/kernels/w8a16.hip): (nt, splits)
+# per projection and row bucket, from the cold-weight sweep of bench/w8_probe.py --sweep
+# on MI355X at 1 / 16 / 50 / 64 rows (profiles/w8a16_r12.log; us with the slab tail,
+# the bf16 plan's kernel in brackets): qkv 8.5 / 9.4 / 14.5 / 15.4 [10.0 / 11.0 / 16.9 /
+# 17.5], o 7.3 / 7.9 / 11.5 / 12.1 [9.2 / 9.7 / 13.0 / 13.5], gate_up + SiLU 22.5 / 22.9 /
+# 29.3 / 29.5 [41.2 / 44.8 / 45.5 / 45.0], down 12.9 / 14.0 / 23.7 / 24.9 [22.3 / 22.8 /
+# 26.6 / 27.8].  The 8 and 32 buckets were not swept and take their neighbour's entry.
+# down at 50 / 64 rows keeps 4 splits although 8 measured 1.4 us faster cold: doubled
+# slabs cost the add + RMSNorm that reduces them more than that
+# (profiles/ab_xr8_r03.log).  gate_up always runs unsplit on two tiles per wave, which
+# is the kernel's SiLU epilogue.
+W8_ROWS = 64
+W8_PLAN = {
+    "qkv": {1: (1, 4), 8: (1, 4), 16: (1, 4), 32: (2, 4), 64: (2, 4)},
+    "o": {1: (2, 8), 8: (1, 4), 16: (1, 4), 32: (1, 4), 64: (1, 4)},
+    "gu": {1: (2, 1), 8: (2, 1), 16: (2, 1), 32: (2, 1), 64: (2, 1)},
+    "down": {1: (1, 8), 8: (1, 8), 16: (1, 8), 32: (1, 4), 64: (1, 4)},
+}
+# Above W8_ROWS rows: w8_packed_gemm.hip, (row limit, tile cfg, split-K); one tile is
+# built (cfg 0 = 128 x 256).  Splits from the same sweep at 145 / 300 / 512 / 1,024 rows
+# (us, packed_gemm on the bf16 image in brackets): qkv 29.6 / 42.4 / 45.8 / 63.2 [23.1 /
+# 35.4 / 44.4 / 67.2], o 25.4 / 30.6 / 34.4 / 48.5 [19.2 / 24.7 / 32.1 / 48.8], gate_up +
+# SiLU 62.4 / 118.6 / 123.6 / 237.9 [58.5 / 90.8 / 109.6 / 210.0], down 42.2 / 62.4 /
+# 68.6 / 115.8 [36.4 / 54.6 / 70.1 / 114.2].  <= 128 rows keep W4PG_PLAN's splits.
+W8PG_PLAN = {
+    "qkv": ((128, 0, 8), (256, 0, 4), (512, 0, 2), (1 << 30, 0, 1)),
+    "o": ((256, 0, 8), (512, 0, 4), (2047, 0, 2), (1 << 30, 0, 1)),
+    "gu": ((128, 0, 2), (1 << 30, 0, 1)),
+    "down": ((128, 0, 16), (256, 0, 8), (512, 0, 4), (2047, 0, 2), (1 << 30, 0, 1)),
+}
+
+
+def w8_cfg(proj: str, rows: int, n: int, k: int) -> Tuple[int, int]:
+    """(nt, splits) of a W8 decode GEMM (<= W8_ROWS rows): the bucket's entry with its
+    splits halved until K / splits is a whole number of 256-wide chunks."""
+    nt, sp = W8_PLAN[proj][next(m for m in _M_BUCKETS if m >= rows)]
+    while sp > 1 and k % (256 * sp):
+        sp //= 2
+    return nt, sp
+
+
+def w8pg_cfg(proj: str, rows: int, n: int, k: int, ws_elems: Optional[int] = None) -> Tuple[int, int]:
+    """(tile cfg, splits) of a W8 GEMM above W8_ROWS rows: the plan's splits halved until
+    they divide K into whole 64-wide k-steps and (``ws_elems`` given) the fp32 slabs
+    [splits, rows, n] fit the workspace."""
+    for lim, cfg, sp in W8PG_PLAN[proj]:
+        if rows <= lim:
+            break
+    while sp > 1 and (k % (64 * sp) or (ws_elems is not None and sp * rows * n > ws_elems)):
+        sp //= 2
+    return cfg, sp
+
+
 # Projections of >= 64 M weights (Llama-3-70B at TP=1: qkv 10240 x 8192, o 8192 x 8192,
 # down 8192 x 28672) at 33-64 rows: two column tiles per wave (qkv, down) or 8-wave
 # workgroups (o), same splits -- cold-cache us at 50 rows, round 5
@@ -459,8 +515,11 @@ class LlamaModel:
         # "awq" / "w4": layer projections as W4A16 (group 128).  On the GPU only the
         # packed int4 image is kept; the CPU backend holds the dequantized weights.
         self.quant = (quantization or "").lower() or None
-        if self.quant not in (None, "awq", "w4"):
-            raise ValueError(f"unsupported quantization {quantization!r} (awq | w4)")
+        if self.quant not in (None, "awq", "w4", "fp8"):
+            raise ValueError(f"unsupported quantization {quantization!r} (awq | w4 | fp8)")
+        if self.quant == "fp8" and self.tp > 1:
+            raise ValueError("quantization 'fp8' does not support tensor parallelism yet "
+                             f"(tp_size {self.tp}); run it at tp_size 1")
         # W4 above W4_ROWS rows: auto (FT_W4_PREFILL_IMAGE decides) | image | scratch |
         # int4 (w4_packed_gemm.hip on the int4 image; no bf16 copy, no scratch)
         self.w4_prefill = (w4_prefill or "auto").lower()
@@ -550,14 +609,26 @@ class LlamaModel:
         awq = W.is_awq_checkpoint(idx)
         if awq and self.quant is None:
             self.quant = "awq"
+        fp8 = not awq and W.is_fp8_checkpoint(idx)
+        if fp8:
+            if self.quant not in (None, "fp8"):
+                raise ValueError(f"an fp8 checkpoint cannot be served as quantization {self.quant!r}")
+            if self.tp > 1:
+                raise ValueError("fp8 checkpoints do not support tensor parallelism yet "
+                                 f"(tp_size {self.tp}); run them at tp_size 1")
+            self.quant = "fp8"
         shards = []
         for li in range(cfg.num_layers):
-            if awq:
+            if fp8:
+                shards.append(W.load_fp8_layer(cfg, idx, li))
+            elif awq:
                 shards.append(W.load_awq_layer_shard(cfg, idx, li, self.rank, self.tp))
             else:
                 full = W.load_full_layer(idx, li, self.dtype)
                 shards.append(W.shard_full_layer(cfg, full, self.rank, self.tp))
-        if awq:
+        if fp8:
+            self._set_w8_layers(shards)
+        elif awq:
             self._set_w4_layers(shards)
         else:
             self._set_layers(shards)
@@ -572,7 +643,7 @@ class LlamaModel:
         if full_scales is not None:
             self.ckpt_kv_scales = tuple(W.shard_kv_scales(cfg, t, self.rank, self.tp)
                                         for t in full_scales)
-        if not awq:  # AWQ layers arrive quantized
+        if not awq and not fp8:  # AWQ / fp8 layers arrive quantized
             self._quantize_layers()
         self._prepare_packed()
         return self
@@ -606,10 +677,37 @@ class LlamaModel:
                     continue
                 # from the bf16 values on every backend, so the CPU reference and the
                 # GPU hold the same quantized weights
+                if self.quant == "fp8":
+                    self._install_w8(L, proj, *Q.quantize_w8(w.to(torch.bfloat16)))
+                    continue
                 q, z, sc = Q.quantize_w4(w.to(torch.bfloat16))
                 self._install_w4(L, proj, q, z, sc)
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)  # free the bf16 copies as we go
+
+    # ------------------------------------------------------------------ W8A16 (fp8)
+    def _install_w8(self, L: LayerWeights, proj: str, q, s):
+        """One fp8 projection (q float8_e4m3fn [N, K], s fp32 [N]).  GPU: the packed fp8
+        image and its scales are all that stays resident (gate_up interleaved in 16-row
+        groups for the SiLU epilogues; a shape the image cannot hold raises).  CPU
+        reference backend: the dequantized weight q * s in the compute dtype."""
+        if self.device.type == "cuda":
+            if L.q8 is None:
+                L.q8 = {}
+            L.q8[proj] = Q.pack_w8(q.to(self.device), s.to(self.device), gate_up=proj == "gu")
+            setattr(L, _ATTR[proj], None)
+        else:
+            setattr(L, _ATTR[proj], Q.dequantize_w8(q, s).to(self.dtype))
+
+    def _set_w8_layers(self, shards):
+        self.layers = []
+        for sh in shards:
+            L = LayerWeights(wqkv=None, wo=None, wgu=None, wd=None,
+                             ln1=sh["ln1"].to(self.device, self.dtype),
+                             ln2=sh["ln2"].to(self.device, self.dtype))
+            for proj, attr in _ATTR.items():
+                self._install_w8(L, proj, *sh[attr])
+            self.layers.append(L)
 
     def _set_w4_layers(self, shards):
         self.layers = []
@@ -749,6 +847,10 @@ class LlamaModel:
             for proj, q in (L0.q4 or {}).items():
                 need = max(need, max((sp * min(lim, PG_MAX_SLAB_ROWS) * q.n
                                       for lim, _, sp in W4PG_PLAN[proj] if sp > 1), default=0))
+        for proj, q in (L0.q8 or {}).items():   # W8: the decode and the packed plans' slabs
+            need = max(need, max(sp * b * q.n for b, (_, sp) in W8_PLAN[proj].items()))
+            need = max(need, max((sp * min(lim, PG_MAX_SLAB_ROWS) * q.n
+                                  for lim, _, sp in W8PG_PLAN[proj] if sp > 1), default=0))
         self.ws = torch.empty(need, dtype=torch.float32, device=self.device)
         # in-launch split-K tickets (fused ring layer): zeroed,
         # every launch leaves them zeroed
@@ -937,6 +1039,9 @@ class LlamaModel:
         is left as ``splits`` fp32 slabs in self.ws for the fused consumer, else
         (0, y).  For "gu" y is already h = silu(gate) * up."""
         rows = x.shape[0]
+        q8 = L.q8.get(proj) if L.q8 else None
+        if q8 is not None:  # W8A16
+            return self._w8_lin(x, q8, proj)
         q = L.q4.get(proj) if L.q4 else None
         if q is not None:  # W4A16
             il = proj == "gu" and self.w4_gu_il
@@ -991,6 +1096,35 @@ class LlamaModel:
             return 0, ops.silu_mul(Q.w4_packed_gemm(x, q, cfg=cfg), interleaved=False)
         return 0, Q.w4_packed_gemm(x, q, cfg=cfg)
 
+    def _w8_lin(self, x: torch.Tensor, q: "Q.W8Weight", proj: str) -> Tuple[int, Optional[torch.Tensor]]:
+        """y = s * (x q^T) on the fp8 image: w8a16.hip up to W8_ROWS rows (W8_PLAN),
+        w8_packed_gemm.hip above (W8PG_PLAN).  Split-K slabs are left for the fused
+        consumer where _slab_ok allows, else reduced by slab_store; gate_up runs the SiLU
+        epilogue when unsplit, else leaves slabs for slab_silu."""
+        rows = x.shape[0]
+        gu = proj == "gu"
+        ws_elems = self.ws.numel() if self.ws is not None else 0
+        if rows <= W8_ROWS:
+            nt, sp = w8_cfg(proj, rows, q.n, q.k)
+            cfg = None
+        else:
+            cfg, sp = w8pg_cfg(proj, rows, q.n, q.k, ws_elems)
+        if sp > 1 and sp * rows * q.n > ws_elems:
+            sp = 1
+        if sp > 1:
+            if cfg is None:
+                Q.w8_gemm(x, q, ws=self.ws, splits=sp, nt=nt)
+            else:
+                Q.w8_packed_gemm(x, q, ws=self.ws, splits=sp, epi="slab", cfg=cfg)
+            if self._slab_ok(proj, rows):
+                return sp, None
+            y = torch.empty(rows, q.n, dtype=x.dtype, device=x.device)  # odd hidden
+            ops.slab_store(self.ws, sp, rows, q.n, y)
+            return 0, y
+        if cfg is None:
+            return 0, (Q.w8_gemm(x, q, nt=2, silu=True) if gu else Q.w8_gemm(x, q, nt=nt))
+        return 0, Q.w8_packed_gemm(x, q, epi="silu" if gu else "store", cfg=cfg)
+
     def w4_prefill_mode(self) -> Optional[str]:
         """How W4 projections run above W4_ROWS rows: int4 | image | scratch; None for a
         bf16 model and on the CPU backend (dequantized weights)."""
@@ -1017,6 +1151,8 @@ class LlamaModel:
 
         for L in self.layers:
             for q in (L.q4 or {}).values():
+                total += q.nbytes()
+            for q in (L.q8 or {}).values():
                 total += q.nbytes()
             for f in dataclasses.fields(L):
                 v = getattr(L, f.name)

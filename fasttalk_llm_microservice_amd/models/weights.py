@@ -285,6 +285,121 @@ def save_awq_checkpoint(cfg: ModelConfig, full_layers, embed, norm, lm_head, out
         json.dump(hf_cfg, f, indent=1)
 
 
+# --------------------------------------------------------------------------------------
+# fp8 (W8A16) checkpoints: float8_e4m3fn weights with per-channel or per-tensor scales
+# --------------------------------------------------------------------------------------
+# Accepted tensor names per projection (suffix after "model.layers.N.<proj>"): what vLLM
+# writes for --quantization fp8 and AMD Quark FP8 exports.  No real fp8 checkpoint was
+# at hand to check this list against, so parity with one is unpinned and the names are
+# kept in this one table.
+FP8_NAMES = {
+    "weight": ".weight",              # float8_e4m3fn [N, K]
+    "scale": ".weight_scale",         # fp32 scalar, [1], [N] or [N, 1]
+    "ignored": (".input_scale",),     # static activation scales of W8A8 checkpoints
+}
+_FP8_FUSED = {"wqkv": ("q", "k", "v"), "wo": ("o",), "wgu": ("gate", "up"), "wd": ("down",)}
+_fp8_logged_input_scale = False
+
+
+def is_fp8_checkpoint(idx: SafetensorsIndex) -> bool:
+    """The first q_proj weight is float8_e4m3fn and has a weight_scale (with or without
+    a ``quantization_config`` naming quant_method fp8)."""
+    p = "model.layers.0." + _HF_PROJ["q"]
+    if not (idx.has(p + FP8_NAMES["weight"]) and idx.has(p + FP8_NAMES["scale"])):
+        return False
+    return idx.get(p + FP8_NAMES["weight"]).dtype == torch.float8_e4m3fn
+
+
+def _fp8_proj(idx: SafetensorsIndex, base: str):
+    """(q float8_e4m3fn [N, K], s fp32 [N]) of one projection; raises on NaN weight bytes
+    and on scales that are not finite and positive."""
+    from ..ops.quant import fp8_nan_bytes
+
+    q = idx.get(base + FP8_NAMES["weight"])
+    if q.dtype != torch.float8_e4m3fn or q.dim() != 2:
+        raise ValueError(f"{base}{FP8_NAMES['weight']}: expected a 2-D float8_e4m3fn tensor, "
+                         f"got {q.dtype} {tuple(q.shape)}")
+    if bool(fp8_nan_bytes(q).any()):
+        raise ValueError(f"{base}{FP8_NAMES['weight']}: holds NaN bytes")
+    n = q.shape[0]
+    s = idx.get(base + FP8_NAMES["scale"]).float().flatten()
+    if s.numel() not in (1, n):
+        raise ValueError(f"{base}{FP8_NAMES['scale']}: {s.numel()} elements, expected 1 or {n}")
+    if not bool(torch.isfinite(s).all()) or not bool((s > 0).all()):
+        raise ValueError(f"{base}{FP8_NAMES['scale']}: scales must be finite and positive")
+    return q.contiguous(), s.expand(n).contiguous()
+
+
+def load_fp8_layer(cfg: ModelConfig, idx: SafetensorsIndex, layer: int):
+    """One layer of an fp8 checkpoint (TP=1) -> fused projections as (q, s) pairs
+    ([N, K] float8_e4m3fn, [N] fp32) plus the norm weights.  Scales are broadcast to one
+    per output channel, so fusing q/k/v (or gate/up) that carry different per-tensor
+    scales is the concatenation of their channel vectors.  ``input_scale`` tensors are
+    ignored (the activations stay bf16), with one log line."""
+    global _fp8_logged_input_scale
+    p = f"model.layers.{layer}."
+    parts = {}
+    for name, hf in _HF_PROJ.items():
+        parts[name] = _fp8_proj(idx, p + hf)
+        if not _fp8_logged_input_scale and any(idx.has(p + hf + sfx) for sfx in FP8_NAMES["ignored"]):
+            _fp8_logged_input_scale = True
+            import logging
+
+            logging.getLogger(__name__).info(
+                "fp8 checkpoint carries input_scale tensors (static W8A8 activation scales): "
+                "ignored, activations stay bf16")
+    out = {}
+    for attr, names in _FP8_FUSED.items():
+        out[attr] = (torch.cat([parts[m][0].view(torch.uint8) for m in names], 0)
+                     .view(torch.float8_e4m3fn).contiguous(),
+                     torch.cat([parts[m][1] for m in names], 0).contiguous())
+    out["ln1"] = idx.get(p + "input_layernorm.weight")
+    out["ln2"] = idx.get(p + "post_attention_layernorm.weight")
+    return out
+
+
+def save_fp8_checkpoint(cfg: ModelConfig, full_layers, embed, norm, lm_head, out_dir: str,
+                        scale_form: str = "channel", input_scale: bool = False):
+    """Quantize full-precision layers to fp8 e4m3 (ops.quant.quantize_w8) and write them
+    as ``<proj>.weight`` / ``<proj>.weight_scale`` with an HF ``quantization_config``
+    (tests and tooling).  ``scale_form``: "channel" ([N]), "channel2d" ([N, 1]), or one
+    scale per tensor as "tensor" (a scalar) / "tensor1" ([1]).  ``input_scale`` also
+    writes a W8A8-style static activation scale per projection."""
+    from safetensors.torch import load_file, save_file
+
+    from ..ops.quant import FP8, FP8_MAX, quantize_w8
+
+    if scale_form not in ("channel", "channel2d", "tensor", "tensor1"):
+        raise ValueError(f"scale_form {scale_form!r}: channel | channel2d | tensor | tensor1")
+    save_hf_checkpoint(cfg, [], embed, norm, lm_head, out_dir)
+    path = os.path.join(out_dir, "model.safetensors")
+    t = load_file(path)
+    for li, L in enumerate(full_layers):
+        p = f"model.layers.{li}."
+        for name, hf in _HF_PROJ.items():
+            w = L[name].to(torch.bfloat16)
+            if scale_form.startswith("channel"):
+                q, s = quantize_w8(w)
+                s = s.view(-1, 1) if scale_form == "channel2d" else s
+            else:
+                amax = float(w.double().abs().max())
+                s = torch.tensor(amax / FP8_MAX if amax > 0 else 1.0, dtype=torch.float32)
+                q = (w.double() / s.double()).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+                s = s.view(1) if scale_form == "tensor1" else s
+            t[p + hf + FP8_NAMES["weight"]] = q.contiguous()
+            t[p + hf + FP8_NAMES["scale"]] = s.clone().contiguous()
+            if input_scale:
+                t[p + hf + ".input_scale"] = torch.tensor(1.0)
+        t[p + "input_layernorm.weight"] = L["ln1"].contiguous()
+        t[p + "post_attention_layernorm.weight"] = L["ln2"].contiguous()
+    save_file(t, path)
+    with open(os.path.join(out_dir, "config.json")) as f:
+        hf_cfg = json.load(f)
+    hf_cfg["quantization_config"] = {"quant_method": "fp8", "activation_scheme": "dynamic"}
+    with open(os.path.join(out_dir, "config.json"), "w") as f:
+        json.dump(hf_cfg, f, indent=1)
+
+
 def save_hf_checkpoint(cfg: ModelConfig, full_layers, embed, norm, lm_head: Optional[torch.Tensor],
                        out_dir: str, kv_scales: Optional[Dict[str, object]] = None):
     """Write an HF-layout safetensors checkpoint (used by tests and tooling).

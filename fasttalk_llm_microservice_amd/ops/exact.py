@@ -6,8 +6,9 @@ sums of integers below 2**24 are exact in ANY order, on any tiling, with any spl
 For such operands a kernel's output must equal the fp64 product bit for bit, so the
 tests built on this module need no tolerance and survive every re-tiling of a kernel.
 
-* :func:`int_operands` / :func:`w4_int_operands` / :func:`onehot_operands` /
-  :func:`silu_operands` build the operands and ASSERT the exactness bound.
+* :func:`int_operands` / :func:`w4_int_operands` / :func:`w8_int_operands` /
+  :func:`onehot_operands` / :func:`silu_operands` build the operands and ASSERT the
+  exactness bound.
 * :func:`bf16_ulp_diff` measures bf16 outputs that cannot be exact (SiLU, norms).
 * :func:`guarded` / :func:`guarded_flat` embed a buffer in a larger allocation with a
   fixed bit pattern and check that a launch left everything outside it untouched.
@@ -149,6 +150,34 @@ def w4_int_operands(m: int, n: int, k: int, x_max: int = 2, s_exp: int = -7, n_s
     q, z, s = q.to(device), z.to(device), s.to(device)
     assert_w4_bound(x, q, z, s)
     return x, q, z, s, x.double() @ w4_dequant_exact(q, z, s).t()
+
+
+# ---------------------------------------------------------------------------------
+# W8A16: fp8 e4m3 q holding small integers, power-of-two channel scales
+# ---------------------------------------------------------------------------------
+
+def w8_int_operands(m: int, n: int, k: int, x_max: int = 7, q_max: int = 15, s_exp: int = -6,
+                    n_scales: int = 3, seed: int = 0, device="cpu"):
+    """(x [m, k] bf16, q float8_e4m3fn [n, k], s fp32 [n], exact [m, n] fp64): x integers in
+    [-x_max, x_max], q integers in [-q_max, q_max] (e4m3 holds every integer up to 16
+    exactly; asserted), s per output channel one of ``n_scales`` adjacent powers of two
+    from 2**s_exp, all of them used; exact = x (q s)^T.  The W8 kernels accumulate
+    sum_k x q (integers below 2**24, asserted) and scale the sum once by a power of two,
+    so slabs and their sum in any order are exact.  Pack with ``quant.pack_w8(q, s)``."""
+    assert q_max <= 16 and n >= n_scales
+    g = torch.Generator().manual_seed(seed)
+    xd = _randint(-x_max, x_max, (m, k), g).double()
+    qd = _randint(-q_max, q_max, (n, k), g).double()
+    e = _randint(0, n_scales - 1, (n,), g)
+    e[:n_scales] = torch.arange(n_scales)
+    s = torch.pow(2.0, (s_exp + e).double()).float()
+    q = qd.to(torch.float8_e4m3fn)
+    assert torch.equal(q.double(), qd), "q does not round-trip through e4m3"
+    assert_bf16_exact(xd, "x")
+    x = xd.to(torch.bfloat16).to(device)
+    assert_exact_bound(x, qd.to(device), 1.0)
+    q, s = q.to(device), s.to(device)
+    return x, q, s, x.double() @ (q.double() * s.double().unsqueeze(-1)).t()
 
 
 # ---------------------------------------------------------------------------------

@@ -14,6 +14,11 @@ reference's default model needs (``hugging-quants/Meta-Llama-3.1-8B-Instruct-AWQ
 * :func:`pack_w4`: (q, z, s) -> the MFMA-fragment image ``w4a16.hip`` streams.
 * :class:`W4Weight` holds one packed projection; :func:`w4_gemm` / :func:`w4_dequant`
   dispatch to the HIP kernels, or to a dequantize + matmul reference on the CPU.
+
+W8A16 (fp8 e4m3 weights, one fp32 scale per output channel; vLLM's
+``--quantization fp8``) follows below with the same shape of API:
+:func:`quantize_w8` / :func:`dequantize_w8`, :func:`pack_w8` / :func:`unpack_w8`,
+:class:`W8Weight`, :func:`w8_gemm` (M <= 64) and :func:`w8_packed_gemm` (any M).
 """
 from __future__ import annotations
 
@@ -213,4 +218,208 @@ def w4_packed_gemm(x: torch.Tensor, w: W4Weight, out=None, ws=None, splits: int 
     if code != 1 and out is None:
         out = torch.empty(x.shape[0], w.n // 2 if code == 2 else w.n, dtype=x.dtype, device=x.device)
     native().w4_packed_gemm(x, w.wq, w.sz, w.n, out, ws, splits, code, cfg)
+    return ws if code == 1 else out
+
+
+# ==================================================================================
+# W8A16: fp8 e4m3 (OCP, torch.float8_e4m3fn) weights, one fp32 scale per output channel
+# ==================================================================================
+# The numerics every kernel, CPU fallback and test uses:
+#   y[m, n] = s[n] * sum_k x[m, k] * q[n, k]
+# q widened to bf16 (every e4m3 value is exact in bf16), products on the bf16 MFMA with
+# fp32 accumulation, the scale applied once to the fp32 accumulator (to each slab under
+# split-K), then one rounding to bf16 (or SiLU * up in fp32, then one rounding).  No
+# per-weight multiply, no bf16-rounded q * s.
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+W8_KSTEP = 64          # k-values per image block: two 16x16x32 MFMAs
+
+
+@dataclasses.dataclass
+class W8Weight:
+    wq: torch.Tensor      # uint8 [N/16 * K/64 * 64 * 16]  fp8 bytes in fragment order
+    scale: torch.Tensor   # fp32 [N]  (image row order)
+    n: int
+    k: int
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        return (self.n, self.k)
+
+    def nbytes(self) -> int:
+        return self.wq.numel() + self.scale.numel() * 4
+
+
+def fp8_nan_bytes(q: torch.Tensor) -> torch.Tensor:
+    """bool mask of the e4m3 NaN encodings (0x7F, 0xFF) in an fp8 / uint8 tensor."""
+    return (q.view(torch.uint8) & 0x7F) == 0x7F
+
+
+def quantize_w8(w: torch.Tensor):
+    """[N, K] float -> (q float8_e4m3fn [N, K], s fp32 [N]) with w ~= q * s[:, None]:
+    round to nearest, s = absmax / 448 per row (1 for an all-zero row)."""
+    # fp64: correctly rounded on every backend, so a GPU and a CPU quantization of
+    # the same weights agree bit for bit (as quantize_w4)
+    wd = w.double()
+    amax = wd.abs().amax(-1)
+    s = (amax / FP8_MAX).float()
+    s = torch.where(s > 0, s, torch.ones_like(s))
+    # clamp BEFORE the cast: an out-of-range value becomes NaN, not the maximum
+    q = (wd / s.double().unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+    return q, s
+
+
+def dequantize_w8(q: torch.Tensor, s: torch.Tensor, dtype: torch.dtype = torch.float32):
+    """q * s[:, None]; exact in fp64, one rounding in any other dtype."""
+    if dtype == torch.float64:
+        return q.double() * s.double().unsqueeze(-1)
+    return (q.float() * s.float().unsqueeze(-1)).to(dtype)
+
+
+def _interleave16(t: torch.Tensor) -> torch.Tensor:
+    """Gate rows then up rows -> 16 gate rows, their 16 up rows, ... (ops.interleave_gate_up
+    with nh = 1) along dim 0 of a [2I, ...] tensor."""
+    two_i = t.shape[0]
+    inter = two_i // 2
+    assert inter % 16 == 0, "the gate_up interleave needs inter % 16 == 0"
+    g = t[:inter].reshape(inter // 16, 16, *t.shape[1:])
+    u = t[inter:].reshape(inter // 16, 16, *t.shape[1:])
+    return torch.stack([g, u], dim=1).reshape(t.shape)
+
+
+def _deinterleave16(t: torch.Tensor) -> torch.Tensor:
+    two_i = t.shape[0]
+    v = t.reshape(two_i // 32, 2, 16, *t.shape[1:])
+    return torch.cat([v[:, 0].reshape(two_i // 2, *t.shape[1:]),
+                      v[:, 1].reshape(two_i // 2, *t.shape[1:])], 0)
+
+
+def pack_w8(q: torch.Tensor, s: torch.Tensor, gate_up: bool = False) -> W8Weight:
+    """(q, s) -> the kernel image.  wq[tile][step][lane][16], lane = g * 16 + r: byte
+    8 * half + e of a lane's 16 is k = 64 step + 16 g + 8 half + e of column 16 tile + r,
+    so one 16-byte load per lane holds the 16 k-values the lane feeds to the two
+    v_mfma_f32_16x16x32_bf16 (half 0, half 1) of a 64-wide k-step, a wave instruction
+    reads the 1 KiB block of one (tile, step), and a column tile's blocks follow each
+    other along K.  ``scale`` is s in image row order.  ``gate_up``: rows (gate then up)
+    and their scales are first interleaved in 16-row groups (ops.interleave_gate_up(w, 1)),
+    the order the SiLU epilogues and slab_silu(interleaved=True) expect."""
+    n, k = q.shape
+    if n % 16 or k % W8_KSTEP:
+        raise ValueError(f"W8 needs N % 16 == 0 and K % 64 == 0 (N = {n}, K = {k})")
+    if q.dtype != FP8:
+        raise ValueError(f"pack_w8: q must be float8_e4m3fn, not {q.dtype}")
+    if gate_up and n % 32:
+        raise ValueError(f"pack_w8: a gate_up image needs N % 32 == 0 (N = {n})")
+    b = q.view(torch.uint8)
+    s = s.float().reshape(n)
+    if gate_up:
+        b, s = _interleave16(b), _interleave16(s)
+    # (tile, r, step, g, byte) -> (tile, step, g, r, byte)
+    wq = b.reshape(n // 16, 16, k // 64, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+    return W8Weight(wq, s.contiguous(), n, k)
+
+
+def unpack_w8(w: W8Weight, gate_up: bool = False):
+    """Inverse of :func:`pack_w8` (tests, checkpoint export): (q float8_e4m3fn [N, K], s)."""
+    n, k = w.n, w.k
+    b = w.wq.view(n // 16, k // 64, 4, 16, 16).permute(0, 3, 1, 2, 4).contiguous().view(n, k)
+    s = w.scale
+    if gate_up:
+        b, s = _deinterleave16(b), _deinterleave16(s)
+    return b.contiguous().view(FP8), s.contiguous()
+
+
+W8_NTS = (1, 2, 4)     # column tiles per wave the decode kernel is built for
+
+
+def _w8_ref(x: torch.Tensor, w: W8Weight) -> torch.Tensor:
+    """The contract in fp32 on the CPU: s[n] * sum_k x q, image row order."""
+    q, s = unpack_w8(w)
+    return (x.float() @ q.float().t()) * s.float()
+
+
+def w8_gemm(x: torch.Tensor, w: W8Weight, out=None, ws=None, splits: int = 1, nt: int = 2,
+            silu: bool = False):
+    """y = s * (x q^T) for M <= 64 rows (csrc/kernels/w8a16.hip).  With ``ws`` the kernel
+    leaves fp32 slabs ([splits, M, N], each already scaled) for a fused epilogue and
+    returns ``ws``; otherwise it returns bf16 ``out``.  ``nt``: 16-column tiles per wave
+    (1, 2, 4).  ``silu``: h = silu(gate) * up of a ``pack_w8(..., gate_up=True)`` image,
+    [M, N / 2] (nt 2, one split, no workspace)."""
+    m = x.shape[0]
+    if m > 64:
+        raise ValueError(f"w8_gemm: M = {m} > 64 (use w8_packed_gemm)")
+    if nt not in W8_NTS:
+        raise ValueError(f"w8_gemm: nt {nt} not in {W8_NTS}")
+    if splits < 1 or w.k % (256 * splits):
+        raise ValueError(f"w8_gemm: K {w.k} is not a multiple of 256 * splits ({splits})")
+    if silu and (ws is not None or splits != 1 or nt != 2 or w.n % 32):
+        raise ValueError("w8_gemm: the SiLU epilogue is nt 2, one split, bf16 out, N % 32 == 0")
+    if splits > 1 and ws is None:
+        raise ValueError("w8_gemm: splits > 1 needs a workspace")
+    if ws is not None and ws.numel() < splits * m * w.n:
+        raise ValueError(f"w8_gemm: workspace too small ({ws.numel()} < {splits * m * w.n})")
+    if not x.is_cuda:
+        y = _w8_ref(x, w)
+        if ws is not None:   # the whole product in slab 0
+            slabs = ws.view(-1)[:splits * m * w.n].view(splits, m, w.n)
+            slabs.zero_()
+            slabs[0].copy_(y)
+            return ws
+        if silu:
+            g, u = y.view(m, -1, 2, 16).unbind(2)
+            y = (torch.nn.functional.silu(g) * u).reshape(m, -1)
+        y = y.to(x.dtype)
+        if out is not None:
+            out[:m, :y.shape[1]].copy_(y)
+            return out
+        return y
+    from . import native
+
+    if ws is None and out is None:
+        out = torch.empty(m, w.n // 2 if silu else w.n, dtype=x.dtype, device=x.device)
+    native().w8_gemm(x, w.wq, w.scale, w.n, out, ws, splits, nt, silu)
+    return out if ws is None else ws
+
+
+def w8_packed_gemm(x: torch.Tensor, w: W8Weight, out=None, ws=None, splits: int = 1,
+                   epi: str = "store", cfg: int = 0):
+    """y = s * (x q^T) for any row count on the fp8 image
+    (csrc/kernels/w8_packed_gemm.hip), with the decode kernel's numerics.  epi "store":
+    bf16 [M, N]; "slab": fp32 slabs [splits, M, N] in ``ws`` (any split count, each
+    scaled); "silu": silu(gate) * up of a gate_up image -> [M, N / 2].  cfg 0 = the
+    128 x 256 tile.  Returns ``ws`` for slabs, else ``out``."""
+    code = _W4PG_EPI[epi]
+    m = x.shape[0]
+    if cfg != 0:
+        raise ValueError(f"w8_packed_gemm: unknown tile shape cfg {cfg}")
+    if splits < 1 or w.k % (W8_KSTEP * splits):
+        raise ValueError(f"w8_packed_gemm: K {w.k} is not a multiple of 64 * splits ({splits})")
+    if code != 1 and splits != 1:
+        raise ValueError("w8_packed_gemm: splits > 1 leaves slabs (epi='slab')")
+    if code == 2 and w.n % 32:
+        raise ValueError(f"w8_packed_gemm: the SiLU epilogue needs N % 32 == 0 (N = {w.n})")
+    if code == 1 and ws is None:
+        raise ValueError("w8_packed_gemm: slabs need a workspace")
+    if code == 1 and ws.numel() < splits * m * w.n:
+        raise ValueError(f"w8_packed_gemm: workspace too small ({ws.numel()} < {splits * m * w.n})")
+    if not x.is_cuda:
+        y = _w8_ref(x, w)
+        if code == 1:   # the whole product in slab 0
+            slabs = ws.view(-1)[:splits * m * w.n].view(splits, m, w.n)
+            slabs.zero_()
+            slabs[0].copy_(y)
+            return ws
+        if code == 2:
+            g, u = y.view(m, -1, 2, 16).unbind(2)
+            y = (torch.nn.functional.silu(g) * u).reshape(m, -1)
+        y = y.to(x.dtype)
+        if out is not None:
+            out[:m, :y.shape[1]].copy_(y)
+            return out
+        return y
+    from . import native
+
+    if code != 1 and out is None:
+        out = torch.empty(m, w.n // 2 if code == 2 else w.n, dtype=x.dtype, device=x.device)
+    native().w8_packed_gemm(x, w.wq, w.scale, w.n, out, ws, splits, code, cfg)
     return ws if code == 1 else out
