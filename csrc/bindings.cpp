@@ -110,6 +110,12 @@ int ft_w8_gemm(const void* x, int x_stride, int M, const uint8_t* wq, const floa
 int ft_w8_packed_gemm(const void* x, int x_stride, int M, const uint8_t* wq, const float* scale,
                       int N, int K, int splits, int epi, int cfg, void* out, int out_stride,
                       float* ws, long ws_floats, hipStream_t stream);
+int ft_mx4_gemm(const void* x, int x_stride, int M, const uint8_t* wq, const uint8_t* sc, int N,
+                int K, float* ws, long ws_floats, void* out, int out_stride, int splits, int nt,
+                int silu, hipStream_t stream);
+int ft_mx4_packed_gemm(const void* x, int x_stride, int M, const uint8_t* wq, const uint8_t* sc,
+                       int N, int K, int splits, int epi, int cfg, void* out, int out_stride,
+                       float* ws, long ws_floats, hipStream_t stream);
 int ft_pkr_gemm(const void* x, int x_stride, int M, const void* wpk, int N, int K, float* ws,
                 void* out, int out_stride, void* residual, int res_stride, int* tickets,
                 int splits, int nt, int depth, int epi, int norm, int wn, float eps,
@@ -800,6 +806,69 @@ void w8_packed_gemm(at::Tensor x, at::Tensor wq, at::Tensor scale, int64_t N,
   check_rc((int)w8_packed_gemm_rc(x, wq, scale, N, out, ws, splits, epi, cfg), "w8_packed_gemm");
 }
 
+// MXFP4 (W4A16): wq uint8 e2m1 image [N/16][K/128][64][16], sc uint8 e8m0 scale bytes
+// [N/16][K/128][64]; see mx4a16.hip.  Tensors are checked here, every argument the
+// kernels constrain by the launchers before any launch; the *_rc forms return the code.
+void check_mx4(const at::Tensor& wq, const at::Tensor& sc, int64_t N, int64_t K) {
+  check_dev(wq, "wq");
+  check_dev(sc, "sc");
+  TORCH_CHECK(wq.scalar_type() == at::kByte && wq.is_contiguous(), "wq uint8 contiguous");
+  TORCH_CHECK(sc.scalar_type() == at::kByte && sc.is_contiguous(), "sc uint8 contiguous");
+  TORCH_CHECK(N > 0 && K > 0 && K % 32 == 0 && wq.numel() == N * K / 2, "wq size");
+  TORCH_CHECK(sc.numel() == N * K / 32, "sc size");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0, "wq must be 16-B aligned");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(sc.data_ptr()) % 16 == 0, "sc must be 16-B aligned");
+}
+
+// y = x dequant(W)^T for M <= 64 rows (mx4a16.hip); with ws: fp32 slabs [splits, M, N]
+int64_t mx4_gemm_rc(at::Tensor x, at::Tensor wq, at::Tensor sc, int64_t N,
+                    c10::optional<at::Tensor> out, c10::optional<at::Tensor> ws, int64_t splits,
+                    int64_t nt, bool silu) {
+  check_bf16(x, "x");
+  check_rows(x, "x");
+  const int M = (int)x.size(0), K = (int)x.size(1);
+  check_mx4(wq, sc, N, K);
+  float* wsp = nullptr;
+  long ws_floats = 0;
+  void* op = nullptr;
+  int ostride = 0;
+  w8_outputs(out, ws, M, silu ? N / 2 : N, &op, &ostride, &wsp, &ws_floats);
+  return ft_mx4_gemm(x.data_ptr(), (int)x.stride(0), M, wq.data_ptr<uint8_t>(),
+                     sc.data_ptr<uint8_t>(), (int)N, K, wsp, ws_floats, ws.has_value() ? nullptr : op,
+                     ostride, (int)splits, (int)nt, silu ? 1 : 0, cur_stream());
+}
+
+void mx4_gemm(at::Tensor x, at::Tensor wq, at::Tensor sc, int64_t N, c10::optional<at::Tensor> out,
+              c10::optional<at::Tensor> ws, int64_t splits, int64_t nt, bool silu) {
+  check_rc((int)mx4_gemm_rc(x, wq, sc, N, out, ws, splits, nt, silu), "mx4_gemm");
+}
+
+// MXFP4 GEMM for any row count on the same image (mx4_packed_gemm.hip).  epi: 0 bf16 out
+// [M, N] (one split), 1 fp32 slabs ws [splits, M, N], 2 SiLU-mul out [M, N/2].
+int64_t mx4_packed_gemm_rc(at::Tensor x, at::Tensor wq, at::Tensor sc, int64_t N,
+                           c10::optional<at::Tensor> out, c10::optional<at::Tensor> ws,
+                           int64_t splits, int64_t epi, int64_t cfg) {
+  check_bf16(x, "x");
+  check_rows(x, "x");
+  const int M = (int)x.size(0), K = (int)x.size(1);
+  check_mx4(wq, sc, N, K);
+  float* wsp = nullptr;
+  long ws_floats = 0;
+  void* op = nullptr;
+  int ostride = 0;
+  w8_outputs(out, ws, M, epi == 2 ? N / 2 : N, &op, &ostride, &wsp, &ws_floats);
+  return ft_mx4_packed_gemm(x.data_ptr(), (int)x.stride(0), M, wq.data_ptr<uint8_t>(),
+                            sc.data_ptr<uint8_t>(), (int)N, K, (int)splits, (int)epi, (int)cfg,
+                            epi == 1 ? nullptr : op, ostride, epi == 1 ? wsp : nullptr, ws_floats,
+                            cur_stream());
+}
+
+void mx4_packed_gemm(at::Tensor x, at::Tensor wq, at::Tensor sc, int64_t N,
+                     c10::optional<at::Tensor> out, c10::optional<at::Tensor> ws, int64_t splits,
+                     int64_t epi, int64_t cfg) {
+  check_rc((int)mx4_packed_gemm_rc(x, wq, sc, N, out, ws, splits, epi, cfg), "mx4_packed_gemm");
+}
+
 void w4_dequant(at::Tensor wq, at::Tensor sz, at::Tensor out) {
   check_bf16(out, "out");
   TORCH_CHECK(out.dim() == 2 && out.is_contiguous(), "out [N, K] contiguous");
@@ -1299,6 +1368,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w8_gemm_rc", &w8_gemm_rc);
   m.def("w8_packed_gemm", &w8_packed_gemm);
   m.def("w8_packed_gemm_rc", &w8_packed_gemm_rc);
+  m.def("mx4_gemm", &mx4_gemm);
+  m.def("mx4_gemm_rc", &mx4_gemm_rc);
+  m.def("mx4_packed_gemm", &mx4_packed_gemm);
+  m.def("mx4_packed_gemm_rc", &mx4_packed_gemm_rc);
   m.def("skinny_gemm_xr", &skinny_gemm_xr, py::arg("x"), py::arg("w"), py::arg("out") = py::none(),
         py::arg("ws") = py::none(), py::arg("splits") = 1, py::arg("nt") = 2, py::arg("epi") = 0,
         py::arg("nw") = 4);

@@ -68,6 +68,7 @@ class EngineConfig:
     max_restarts: int = 3              # separate-process engines: respawns after a replica dies
     # None | "awq" | "w4" (W4A16, group 128; --quantization awq) | "fp8" (W8A16: e4m3
     # weights with per-channel scales, --quantization fp8; tp_size 1, not batch-invariant)
+    # | "mxfp4" (W4A16: OCP MX e2m1 weights, e8m0 block scales; same restrictions)
     quantization: Optional[str] = None
     # a sequence's tokens independent of what else shares its steps (fixed GEMM splits,
     # fixed-piece attention partitions; TP=1, bf16; slower decode attention)
@@ -101,12 +102,12 @@ class EngineConfig:
     def check_quantization(self) -> Optional[str]:
         """What fp8 weights cannot be combined with yet; ValueError for those."""
         q = (self.quantization or "").strip().lower() or None
-        if q == "fp8":
+        if q in ("fp8", "mxfp4"):
             if self.tp_size > 1:
-                raise ValueError("quantization='fp8' does not support tensor parallelism yet "
+                raise ValueError(f"quantization='{q}' does not support tensor parallelism yet "
                                  f"(tp_size={self.tp_size})")
             if self.batch_invariant:
-                raise ValueError("quantization='fp8' does not support batch-invariant mode yet "
+                raise ValueError(f"quantization='{q}' does not support batch-invariant mode yet "
                                  "(ENGINE_BATCH_INVARIANT=1)")
         return q
 

@@ -357,11 +357,15 @@ class ModelRunner:
             self.weights_info["w4_prefill"] = w4_mode
         if self.model.quant == "fp8":   # only then: every other engine reports what it did
             self.weights_info["quantization"] = "fp8"
-        log.info("weights ready in %.1fs: %.3f GB resident%s%s", time.time() - t0,
+        if self.model.quant == "mxfp4":
+            self.weights_info["quantization"] = "mxfp4"
+        log.info("weights ready in %.1fs: %.3f GB resident%s%s%s", time.time() - t0,
                  self.weights_info["weights_resident_gb"],
                  f", W4 above 64 rows: {w4_mode}" if w4_mode else "",
                  ", quantization fp8 (e4m3 weights, per-channel scales; bench.py still labels "
-                 "the dtype bf16)" if self.model.quant == "fp8" else "")
+                 "the dtype bf16)" if self.model.quant == "fp8" else "",
+                 ", quantization mxfp4 (e2m1 weights, e8m0 scales per 32 k; bench.py still "
+                 "labels the dtype bf16)" if self.model.quant == "mxfp4" else "")
 
         # batch-invariant numerics (cfg.batch_invariant): rows of a step up to the token
         # budget plus a decode row per sequence

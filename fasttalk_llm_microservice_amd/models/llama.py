@@ -90,6 +90,9 @@ class LayerWeights:
     # W8A16 (fp8 e4m3, per-channel scales) projections by name, GPU only: the fp8 image
     # is the only resident copy of a projection
     q8: Optional[dict] = None
+    # MXFP4 (e2m1 codes, e8m0 block scales) projections by name, GPU only: the image and
+    # its scale bytes are the only resident copy of a projection
+    q4x: Optional[dict] = None
 
 
 _ATTR = {"qkv": "wqkv", "o": "wo", "gu": "wgu", "down": "wd"}
@@ -454,6 +457,59 @@ def w8pg_cfg(proj: str, rows: int, n: int, k: int, ws_elems: Optional[int] = Non
     return cfg, sp
 
 
+# MXFP4 (e2m1 weights, one e8m0 scale per 32 k; csrc/kernels/mx4a16.hip): (nt, splits) per
+# projection and row bucket, from the cold-weight sweep of bench/mx4_probe.py --sweep on
+# MI355X at 1 / 16 / 50 / 64 rows (profiles/mxfp4_r13.log; us with the slab tail, the W8
+# kernel at its plan in brackets): qkv 7.0 / 8.0 / 13.3 / 13.9 [8.5 / 9.5 / 14.3 / 15.3],
+# o 6.3 / 7.0 / 10.3 / 11.0 [7.2 / 7.9 / 11.6 / 12.3], gate_up + SiLU 17.5 / 17.9 / 27.5 /
+# 27.5 [23.1 / 23.4 / 29.5 / 29.7], down 11.5 / 12.6 / 19.3 / 20.0 [13.5 / 14.6 / 24.1 /
+# 25.1].  The tables started as copies of W8_PLAN; the sweep changed one entry: qkv at
+# 50 / 64 rows runs (1, 2) (13.3 / 13.9 us against 14.1 / 15.1 for W8's (2, 4)).  The 8
+# and 32 buckets were not swept and take their neighbour's entry.  gate_up stays unsplit
+# on two tiles per wave (the kernel's SiLU epilogue) although (1, 4) + slab_silu measured
+# 16.1 against 17.5 us at 1 row: one sweep of 3 repetitions, not confirmed in an engine run.
+MX4_ROWS = 64
+MX4_PLAN = {
+    "qkv": {1: (1, 4), 8: (1, 4), 16: (1, 4), 32: (1, 2), 64: (1, 2)},
+    "o": {1: (2, 8), 8: (1, 4), 16: (1, 4), 32: (1, 4), 64: (1, 4)},
+    "gu": {1: (2, 1), 8: (2, 1), 16: (2, 1), 32: (2, 1), 64: (2, 1)},
+    "down": {1: (1, 8), 8: (1, 8), 16: (1, 8), 32: (1, 4), 64: (1, 4)},
+}
+# Above MX4_ROWS rows: mx4_packed_gemm.hip, (row limit, tile cfg, split-K); one tile is
+# built (cfg 0 = 128 x 256).  The same sweep at 145 / 300 / 512 / 1,024 rows kept W8PG_PLAN's
+# splits (every "best" within 3% of them; us, packed_gemm on the bf16 image in brackets):
+# qkv 25.6 / 36.3 / 38.8 / 57.3 [23.7 / 35.3 / 43.0 / 66.7], o 21.4 / 24.4 / 28.3 / 41.9
+# [19.2 / 24.5 / 32.0 / 47.3], gate_up + SiLU 57.0 / 110.6 / 113.5 / 222.8 [57.7 / 85.5 /
+# 105.5 / 210.5], down 34.8 / 56.3 / 62.2 / 110.6 [35.8 / 53.0 / 70.3 / 114.0].
+MX4PG_PLAN = {
+    "qkv": ((128, 0, 8), (256, 0, 4), (512, 0, 2), (1 << 30, 0, 1)),
+    "o": ((256, 0, 8), (512, 0, 4), (2047, 0, 2), (1 << 30, 0, 1)),
+    "gu": ((128, 0, 2), (1 << 30, 0, 1)),
+    "down": ((128, 0, 16), (256, 0, 8), (512, 0, 4), (2047, 0, 2), (1 << 30, 0, 1)),
+}
+
+
+def mx4_cfg(proj: str, rows: int, n: int, k: int) -> Tuple[int, int]:
+    """(nt, splits) of an MX4 decode GEMM (<= MX4_ROWS rows): the bucket's entry with its
+    splits halved until K / splits is a whole number of 256-wide chunks."""
+    nt, sp = MX4_PLAN[proj][next(m for m in _M_BUCKETS if m >= rows)]
+    while sp > 1 and k % (256 * sp):
+        sp //= 2
+    return nt, sp
+
+
+def mx4pg_cfg(proj: str, rows: int, n: int, k: int, ws_elems: Optional[int] = None) -> Tuple[int, int]:
+    """(tile cfg, splits) of an MX4 GEMM above MX4_ROWS rows: the plan's splits halved
+    until they divide K into whole 128-wide k-steps and (``ws_elems`` given) the fp32
+    slabs [splits, rows, n] fit the workspace."""
+    for lim, cfg, sp in MX4PG_PLAN[proj]:
+        if rows <= lim:
+            break
+    while sp > 1 and (k % (128 * sp) or (ws_elems is not None and sp * rows * n > ws_elems)):
+        sp //= 2
+    return cfg, sp
+
+
 # Projections of >= 64 M weights (Llama-3-70B at TP=1: qkv 10240 x 8192, o 8192 x 8192,
 # down 8192 x 28672) at 33-64 rows: two column tiles per wave (qkv, down) or 8-wave
 # workgroups (o), same splits -- cold-cache us at 50 rows, round 5
@@ -515,10 +571,10 @@ class LlamaModel:
         # "awq" / "w4": layer projections as W4A16 (group 128).  On the GPU only the
         # packed int4 image is kept; the CPU backend holds the dequantized weights.
         self.quant = (quantization or "").lower() or None
-        if self.quant not in (None, "awq", "w4", "fp8"):
-            raise ValueError(f"unsupported quantization {quantization!r} (awq | w4 | fp8)")
-        if self.quant == "fp8" and self.tp > 1:
-            raise ValueError("quantization 'fp8' does not support tensor parallelism yet "
+        if self.quant not in (None, "awq", "w4", "fp8", "mxfp4"):
+            raise ValueError(f"unsupported quantization {quantization!r} (awq | w4 | fp8 | mxfp4)")
+        if self.quant in ("fp8", "mxfp4") and self.tp > 1:
+            raise ValueError(f"quantization '{self.quant}' does not support tensor parallelism yet "
                              f"(tp_size {self.tp}); run it at tp_size 1")
         # W4 above W4_ROWS rows: auto (FT_W4_PREFILL_IMAGE decides) | image | scratch |
         # int4 (w4_packed_gemm.hip on the int4 image; no bf16 copy, no scratch)
@@ -617,16 +673,28 @@ class LlamaModel:
                 raise ValueError("fp8 checkpoints do not support tensor parallelism yet "
                                  f"(tp_size {self.tp}); run them at tp_size 1")
             self.quant = "fp8"
+        mx4 = not awq and not fp8 and W.is_mx4_checkpoint(idx)
+        if mx4:
+            if self.quant not in (None, "mxfp4"):
+                raise ValueError(f"an MXFP4 checkpoint cannot be served as quantization {self.quant!r}")
+            if self.tp > 1:
+                raise ValueError("MXFP4 checkpoints do not support tensor parallelism yet "
+                                 f"(tp_size {self.tp}); run them at tp_size 1")
+            self.quant = "mxfp4"
         shards = []
         for li in range(cfg.num_layers):
-            if fp8:
+            if mx4:
+                shards.append(W.load_mx4_layer(cfg, idx, li))
+            elif fp8:
                 shards.append(W.load_fp8_layer(cfg, idx, li))
             elif awq:
                 shards.append(W.load_awq_layer_shard(cfg, idx, li, self.rank, self.tp))
             else:
                 full = W.load_full_layer(idx, li, self.dtype)
                 shards.append(W.shard_full_layer(cfg, full, self.rank, self.tp))
-        if fp8:
+        if mx4:
+            self._set_mx4_layers(shards)
+        elif fp8:
             self._set_w8_layers(shards)
         elif awq:
             self._set_w4_layers(shards)
@@ -643,7 +711,7 @@ class LlamaModel:
         if full_scales is not None:
             self.ckpt_kv_scales = tuple(W.shard_kv_scales(cfg, t, self.rank, self.tp)
                                         for t in full_scales)
-        if not awq and not fp8:  # AWQ / fp8 layers arrive quantized
+        if not awq and not fp8 and not mx4:  # AWQ / fp8 / MXFP4 layers arrive quantized
             self._quantize_layers()
         self._prepare_packed()
         return self
@@ -680,6 +748,9 @@ class LlamaModel:
                 if self.quant == "fp8":
                     self._install_w8(L, proj, *Q.quantize_w8(w.to(torch.bfloat16)))
                     continue
+                if self.quant == "mxfp4":
+                    self._install_mx4(L, proj, *Q.quantize_mx4(w.to(torch.bfloat16)))
+                    continue
                 q, z, sc = Q.quantize_w4(w.to(torch.bfloat16))
                 self._install_w4(L, proj, q, z, sc)
             if self.device.type == "cuda":
@@ -707,6 +778,33 @@ class LlamaModel:
                              ln2=sh["ln2"].to(self.device, self.dtype))
             for proj, attr in _ATTR.items():
                 self._install_w8(L, proj, *sh[attr])
+            self.layers.append(L)
+
+    # ------------------------------------------------------------------ MXFP4
+    def _install_mx4(self, L: LayerWeights, proj: str, codes, sb, name: str = "scale bytes"):
+        """One MXFP4 projection (codes uint8 [N, K], scale bytes uint8 [N, K/32]).  GPU: the
+        packed image and its scale bytes are all that stays resident (gate_up interleaved
+        in 16-row groups for the SiLU epilogues; a shape the image cannot hold or a scale
+        byte outside [2, 252] raises).  CPU reference backend: the dequantized weight in
+        the compute dtype (exact in bf16)."""
+        if self.device.type == "cuda":
+            if L.q4x is None:
+                L.q4x = {}
+            L.q4x[proj] = Q.pack_mx4(codes.to(self.device), sb.to(self.device), gate_up=proj == "gu",
+                                     name=name)
+            setattr(L, _ATTR[proj], None)
+        else:
+            Q.mx4_check_scale_bytes(sb, name)
+            setattr(L, _ATTR[proj], Q.dequantize_mx4(codes, sb).to(self.dtype))
+
+    def _set_mx4_layers(self, shards):
+        self.layers = []
+        for li, sh in enumerate(shards):
+            L = LayerWeights(wqkv=None, wo=None, wgu=None, wd=None,
+                             ln1=sh["ln1"].to(self.device, self.dtype),
+                             ln2=sh["ln2"].to(self.device, self.dtype))
+            for proj, attr in _ATTR.items():
+                self._install_mx4(L, proj, *sh[attr], name=f"layer {li} {proj} weight_scale")
             self.layers.append(L)
 
     def _set_w4_layers(self, shards):
@@ -851,6 +949,10 @@ class LlamaModel:
             need = max(need, max(sp * b * q.n for b, (_, sp) in W8_PLAN[proj].items()))
             need = max(need, max((sp * min(lim, PG_MAX_SLAB_ROWS) * q.n
                                   for lim, _, sp in W8PG_PLAN[proj] if sp > 1), default=0))
+        for proj, q in (L0.q4x or {}).items():   # MXFP4: the decode and the packed plans' slabs
+            need = max(need, max(sp * b * q.n for b, (_, sp) in MX4_PLAN[proj].items()))
+            need = max(need, max((sp * min(lim, PG_MAX_SLAB_ROWS) * q.n
+                                  for lim, _, sp in MX4PG_PLAN[proj] if sp > 1), default=0))
         self.ws = torch.empty(need, dtype=torch.float32, device=self.device)
         # in-launch split-K tickets (fused ring layer): zeroed,
         # every launch leaves them zeroed
@@ -1042,6 +1144,9 @@ class LlamaModel:
         q8 = L.q8.get(proj) if L.q8 else None
         if q8 is not None:  # W8A16
             return self._w8_lin(x, q8, proj)
+        q4x = L.q4x.get(proj) if L.q4x else None
+        if q4x is not None:  # MXFP4
+            return self._mx4_lin(x, q4x, proj)
         q = L.q4.get(proj) if L.q4 else None
         if q is not None:  # W4A16
             il = proj == "gu" and self.w4_gu_il
@@ -1125,6 +1230,35 @@ class LlamaModel:
             return 0, (Q.w8_gemm(x, q, nt=2, silu=True) if gu else Q.w8_gemm(x, q, nt=nt))
         return 0, Q.w8_packed_gemm(x, q, epi="silu" if gu else "store", cfg=cfg)
 
+    def _mx4_lin(self, x: torch.Tensor, q: "Q.MX4Weight", proj: str) -> Tuple[int, Optional[torch.Tensor]]:
+        """y = x dequant(W)^T on the MXFP4 image: mx4a16.hip up to MX4_ROWS rows (MX4_PLAN),
+        mx4_packed_gemm.hip above (MX4PG_PLAN).  Split-K slabs are left for the fused
+        consumer where _slab_ok allows, else reduced by slab_store; gate_up runs the SiLU
+        epilogue when unsplit, else leaves slabs for slab_silu."""
+        rows = x.shape[0]
+        gu = proj == "gu"
+        ws_elems = self.ws.numel() if self.ws is not None else 0
+        if rows <= MX4_ROWS:
+            nt, sp = mx4_cfg(proj, rows, q.n, q.k)
+            cfg = None
+        else:
+            cfg, sp = mx4pg_cfg(proj, rows, q.n, q.k, ws_elems)
+        if sp > 1 and sp * rows * q.n > ws_elems:
+            sp = 1
+        if sp > 1:
+            if cfg is None:
+                Q.mx4_gemm(x, q, ws=self.ws, splits=sp, nt=nt)
+            else:
+                Q.mx4_packed_gemm(x, q, ws=self.ws, splits=sp, epi="slab", cfg=cfg)
+            if self._slab_ok(proj, rows):
+                return sp, None
+            y = torch.empty(rows, q.n, dtype=x.dtype, device=x.device)  # odd hidden
+            ops.slab_store(self.ws, sp, rows, q.n, y)
+            return 0, y
+        if cfg is None:
+            return 0, (Q.mx4_gemm(x, q, nt=2, silu=True) if gu else Q.mx4_gemm(x, q, nt=nt))
+        return 0, Q.mx4_packed_gemm(x, q, epi="silu" if gu else "store", cfg=cfg)
+
     def w4_prefill_mode(self) -> Optional[str]:
         """How W4 projections run above W4_ROWS rows: int4 | image | scratch; None for a
         bf16 model and on the CPU backend (dequantized weights)."""
@@ -1153,6 +1287,8 @@ class LlamaModel:
             for q in (L.q4 or {}).values():
                 total += q.nbytes()
             for q in (L.q8 or {}).values():
+                total += q.nbytes()
+            for q in (L.q4x or {}).values():
                 total += q.nbytes()
             for f in dataclasses.fields(L):
                 v = getattr(L, f.name)

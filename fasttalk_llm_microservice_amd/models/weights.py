@@ -400,6 +400,124 @@ def save_fp8_checkpoint(cfg: ModelConfig, full_layers, embed, norm, lm_head, out
         json.dump(hf_cfg, f, indent=1)
 
 
+# --------------------------------------------------------------------------------------
+# MXFP4 (W4A16) checkpoints: OCP MX e2m1 weights, one e8m0 scale per 32 k-values
+# --------------------------------------------------------------------------------------
+# Accepted tensors per projection (suffix after "model.layers.N.<proj>"), the layout AMD
+# Quark MXFP4 exports use: two codes per byte, the EVEN k in the LOW nibble.  No real
+# MXFP4 export was at hand to check this against, so the names and the nibble order of
+# the checkpoint layout are unpinned; both are kept in this one table and in
+# ops.quant.mx4_from_packed.
+MX4_NAMES = {
+    "weight": ".weight",              # uint8 or float4_e2m1fn_x2 [N, K/2]
+    "scale": ".weight_scale",         # uint8 or float8_e8m0fnu [N, K/32]
+    "ignored": (".input_scale", ".weight_zero_point"),
+}
+_mx4_logged_ignored = False
+
+
+def _mx4_dtypes():
+    w = {torch.uint8}
+    s = {torch.uint8}
+    if hasattr(torch, "float4_e2m1fn_x2"):
+        w.add(torch.float4_e2m1fn_x2)
+    if hasattr(torch, "float8_e8m0fnu"):
+        s.add(torch.float8_e8m0fnu)
+    return w, s
+
+
+def is_mx4_checkpoint(idx: SafetensorsIndex) -> bool:
+    """Layer 0's q_proj has a byte-typed ``weight`` [N, K/2] and a byte-typed
+    ``weight_scale`` [N, K/32] (uint8 or the float4_e2m1fn_x2 / float8_e8m0fnu spellings).
+    fp8 checkpoints carry float8_e4m3fn weights and AWQ ones ``qweight``: no overlap."""
+    p = "model.layers.0." + _HF_PROJ["q"]
+    if not (idx.has(p + MX4_NAMES["weight"]) and idx.has(p + MX4_NAMES["scale"])):
+        return False
+    w, s = idx.get(p + MX4_NAMES["weight"]), idx.get(p + MX4_NAMES["scale"])
+    wd, sd = _mx4_dtypes()
+    return (w.dtype in wd and s.dtype in sd and w.dim() == 2 and s.dim() == 2
+            and w.shape[0] == s.shape[0] and w.shape[1] * 2 == s.shape[1] * 32)
+
+
+def _mx4_proj(idx: SafetensorsIndex, base: str):
+    """(codes uint8 [N, K], scale bytes uint8 [N, K/32]) of one projection; raises on a
+    wrong dtype or shape and on scale bytes outside [2, 252], naming the tensor."""
+    from ..ops.quant import mx4_check_scale_bytes, mx4_from_packed
+
+    wd, sd = _mx4_dtypes()
+    w = idx.get(base + MX4_NAMES["weight"])
+    if w.dtype not in wd or w.dim() != 2:
+        raise ValueError(f"{base}{MX4_NAMES['weight']}: expected a 2-D uint8 / float4_e2m1fn_x2 "
+                         f"tensor, got {w.dtype} {tuple(w.shape)}")
+    s = idx.get(base + MX4_NAMES["scale"])
+    n, k = w.shape[0], w.shape[1] * 2
+    if s.dtype not in sd or tuple(s.shape) != (n, k // 32) or k % 32:
+        raise ValueError(f"{base}{MX4_NAMES['scale']}: expected uint8 / float8_e8m0fnu "
+                         f"{(n, k // 32)}, got {s.dtype} {tuple(s.shape)}")
+    mx4_check_scale_bytes(s, base + MX4_NAMES["scale"])
+    return mx4_from_packed(w.contiguous(), s.contiguous())
+
+
+def load_mx4_layer(cfg: ModelConfig, idx: SafetensorsIndex, layer: int):
+    """One layer of an MXFP4 checkpoint (TP=1) -> fused projections as (codes, scale
+    bytes) pairs plus the norm weights.  Blocks run along K, so fusing q/k/v (or gate/up)
+    is the row concatenation of their codes and scale rows.  Other tensors of a
+    projection (``input_scale``, ...) are ignored, with one log line."""
+    global _mx4_logged_ignored
+    p = f"model.layers.{layer}."
+    parts = {}
+    for name, hf in _HF_PROJ.items():
+        parts[name] = _mx4_proj(idx, p + hf)
+        if not _mx4_logged_ignored and any(idx.has(p + hf + sfx) for sfx in MX4_NAMES["ignored"]):
+            _mx4_logged_ignored = True
+            import logging
+
+            logging.getLogger(__name__).info(
+                "MXFP4 checkpoint carries extra per-projection tensors (input_scale / zero "
+                "points): ignored, activations stay bf16")
+    out = {}
+    for attr, names in _FP8_FUSED.items():
+        out[attr] = (torch.cat([parts[m][0] for m in names], 0).contiguous(),
+                     torch.cat([parts[m][1] for m in names], 0).contiguous())
+    out["ln1"] = idx.get(p + "input_layernorm.weight")
+    out["ln2"] = idx.get(p + "post_attention_layernorm.weight")
+    return out
+
+
+def save_mx4_checkpoint(cfg: ModelConfig, full_layers, embed, norm, lm_head, out_dir: str,
+                        typed: bool = False, input_scale: bool = False):
+    """Quantize full-precision layers to MXFP4 (ops.quant.quantize_mx4) and write them as
+    ``<proj>.weight`` [N, K/2] / ``<proj>.weight_scale`` [N, K/32] with an HF
+    ``quantization_config`` (tests and tooling).  ``typed``: the float4_e2m1fn_x2 /
+    float8_e8m0fnu spellings instead of uint8.  ``input_scale`` also writes a static
+    activation scale per projection (ignored on load)."""
+    from safetensors.torch import load_file, save_file
+
+    from ..ops.quant import mx4_to_packed, quantize_mx4
+
+    save_hf_checkpoint(cfg, [], embed, norm, lm_head, out_dir)
+    path = os.path.join(out_dir, "model.safetensors")
+    t = load_file(path)
+    for li, L in enumerate(full_layers):
+        p = f"model.layers.{li}."
+        for name, hf in _HF_PROJ.items():
+            wb, sb = mx4_to_packed(*quantize_mx4(L[name].to(torch.bfloat16)))
+            if typed:
+                wb, sb = wb.view(torch.float4_e2m1fn_x2), sb.view(torch.float8_e8m0fnu)
+            t[p + hf + MX4_NAMES["weight"]] = wb.contiguous()
+            t[p + hf + MX4_NAMES["scale"]] = sb.contiguous()
+            if input_scale:
+                t[p + hf + ".input_scale"] = torch.tensor(1.0)
+        t[p + "input_layernorm.weight"] = L["ln1"].contiguous()
+        t[p + "post_attention_layernorm.weight"] = L["ln2"].contiguous()
+    save_file(t, path)
+    with open(os.path.join(out_dir, "config.json")) as f:
+        hf_cfg = json.load(f)
+    hf_cfg["quantization_config"] = {"quant_method": "quark", "weight_format": "mxfp4"}
+    with open(os.path.join(out_dir, "config.json"), "w") as f:
+        json.dump(hf_cfg, f, indent=1)
+
+
 def save_hf_checkpoint(cfg: ModelConfig, full_layers, embed, norm, lm_head: Optional[torch.Tensor],
                        out_dir: str, kv_scales: Optional[Dict[str, object]] = None):
     """Write an HF-layout safetensors checkpoint (used by tests and tooling).

@@ -7,8 +7,8 @@ For such operands a kernel's output must equal the fp64 product bit for bit, so 
 tests built on this module need no tolerance and survive every re-tiling of a kernel.
 
 * :func:`int_operands` / :func:`w4_int_operands` / :func:`w8_int_operands` /
-  :func:`onehot_operands` / :func:`silu_operands` build the operands and ASSERT the
-  exactness bound.
+  :func:`mx4_int_operands` / :func:`onehot_operands` / :func:`silu_operands` build the
+  operands and ASSERT the exactness bound.
 * :func:`bf16_ulp_diff` measures bf16 outputs that cannot be exact (SiLU, norms).
 * :func:`guarded` / :func:`guarded_flat` embed a buffer in a larger allocation with a
   fixed bit pattern and check that a launch left everything outside it untouched.
@@ -178,6 +178,38 @@ def w8_int_operands(m: int, n: int, k: int, x_max: int = 7, q_max: int = 15, s_e
     assert_exact_bound(x, qd.to(device), 1.0)
     q, s = q.to(device), s.to(device)
     return x, q, s, x.double() @ (q.double() * s.double().unsqueeze(-1)).t()
+
+
+# ---------------------------------------------------------------------------------
+# MXFP4: e2m1 codes (multiples of 0.5 up to 6), power-of-two block scales
+# ---------------------------------------------------------------------------------
+
+def mx4_int_operands(m: int, n: int, k: int, x_max: int = 7, s_exps=(-2, 0, 2), seed: int = 0,
+                     device="cpu"):
+    """(x [m, k] bf16, codes uint8 [n, k], sb uint8 [n, k / 32], exact [m, n] fp64): x
+    integers in [-x_max, x_max], every e2m1 code 0..15 used, each 32-block scaled by
+    2**e with e one of ``s_exps`` (three exponents two octaves apart, all used); exact =
+    x dequant^T in fp64.  Every weight is an integer multiple of 0.5 * 2**min(s_exps), and
+    the bound sum |x| |w| / unit < 2**24 is asserted on the drawn operands (worst case
+    K * x_max * 12 * 2**(max - min): 2.75 M units at K = 2048), so the fp32 sums of the
+    MX4 kernels are exact in any order.  Pack with ``quant.pack_mx4(codes, sb)``."""
+    from .quant import MX4_BLOCK, dequantize_mx4
+
+    nb = n * (k // MX4_BLOCK)
+    assert k % MX4_BLOCK == 0 and nb >= len(s_exps) and n * k >= 16
+    g = torch.Generator().manual_seed(seed)
+    xd = _randint(-x_max, x_max, (m, k), g).double()
+    codes = _randint(0, 15, (n, k), g).to(torch.uint8)
+    codes.view(-1)[:16] = torch.arange(16, dtype=torch.uint8)
+    pick = _randint(0, len(s_exps) - 1, (nb,), g)
+    pick[:len(s_exps)] = torch.arange(len(s_exps))
+    sb = (torch.tensor(s_exps, dtype=torch.int64)[pick] + 127).to(torch.uint8).view(n, k // MX4_BLOCK)
+    wd = dequantize_mx4(codes, sb, torch.float64)
+    assert_bf16_exact(xd, "x")
+    assert_bf16_exact(wd, "dequantized weight")
+    x = xd.to(torch.bfloat16).to(device)
+    assert_exact_bound(x, wd.to(device), 0.5 * 2.0 ** min(s_exps))
+    return x, codes.to(device), sb.to(device), x.double() @ wd.to(device).t()
 
 
 # ---------------------------------------------------------------------------------

@@ -19,6 +19,11 @@ W8A16 (fp8 e4m3 weights, one fp32 scale per output channel; vLLM's
 ``--quantization fp8``) follows below with the same shape of API:
 :func:`quantize_w8` / :func:`dequantize_w8`, :func:`pack_w8` / :func:`unpack_w8`,
 :class:`W8Weight`, :func:`w8_gemm` (M <= 64) and :func:`w8_packed_gemm` (any M).
+
+MXFP4 (OCP MX e2m1 weights, one e8m0 scale per 32 k-values; AMD Quark MXFP4 exports)
+is the third: :func:`quantize_mx4` / :func:`dequantize_mx4`, :func:`pack_mx4` /
+:func:`unpack_mx4`, :func:`mx4_from_packed`, :class:`MX4Weight`, :func:`mx4_gemm`
+(M <= 64) and :func:`mx4_packed_gemm` (any M).
 """
 from __future__ import annotations
 
@@ -422,4 +427,225 @@ def w8_packed_gemm(x: torch.Tensor, w: W8Weight, out=None, ws=None, splits: int 
     if code != 1 and out is None:
         out = torch.empty(m, w.n // 2 if code == 2 else w.n, dtype=x.dtype, device=x.device)
     native().w8_packed_gemm(x, w.wq, w.scale, w.n, out, ws, splits, code, cfg)
+    return ws if code == 1 else out
+
+
+# ==================================================================================
+# MXFP4 (W4A16): OCP MX e2m1 weights, one e8m0 (power-of-two) scale per 32 k-values
+# ==================================================================================
+# The numerics every kernel, CPU fallback and test uses:
+#   y[m, n] = sum_k x[m, k] * fp4(code[n, k]) * 2^(sb[n, k // 32] - 127)
+# A code is 4 bits: sign in bit 3, magnitude MX4_GRID[code & 7].  With a scale byte in
+# [MX4_SB_MIN, MX4_SB_MAX] every product fp4 * 2^e is a finite NORMAL bf16 (0.5 * 2^-125
+# = 2^-126 is the smallest normal, 6 * 2^125 is finite), so the kernels widen and scale
+# in registers (v_cvt_scalef32_pk_bf16_fp4) and run a plain bf16 MFMA GEMM into fp32 on
+# the dequantized weights: no epilogue scale.  Bytes outside the range are refused
+# (0.5 * 2^(b - 127) goes denormal below, 6 * 2^(b - 127) overflows above, 255 is NaN).
+MX4_BLOCK = 32         # k-values per scale
+MX4_KSTEP = 128        # k-values per image block: four 16x16x32 MFMAs, 4 MX blocks
+MX4_SB_MIN, MX4_SB_MAX = 2, 252
+MX4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MX4_NTS = (1, 2, 4)    # column tiles per wave the decode kernel is built for
+
+
+@dataclasses.dataclass
+class MX4Weight:
+    wq: torch.Tensor      # uint8 [N/16 * K/128 * 64 * 16]  e2m1 nibbles in fragment order
+    sc: torch.Tensor      # uint8 [N/16 * K/128 * 64]       the lanes' e8m0 scale bytes
+    n: int
+    k: int
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        return (self.n, self.k)
+
+    def nbytes(self) -> int:
+        return self.wq.numel() + self.sc.numel()
+
+
+def mx4_check_scale_bytes(sb: torch.Tensor, name: str = "scale bytes") -> None:
+    """ValueError (naming ``name``) unless every e8m0 byte lies in [2, 252]."""
+    b = sb.view(torch.uint8)
+    bad = (b < MX4_SB_MIN) | (b > MX4_SB_MAX)
+    if bool(bad.any()):
+        v = int(b[bad].flatten()[0])
+        raise ValueError(f"{name}: e8m0 scale byte {v} outside [{MX4_SB_MIN}, {MX4_SB_MAX}] "
+                         f"({int(bad.sum())} such bytes; fp4 * 2^(b - 127) would leave the normal "
+                         "bf16 range, 255 is NaN)")
+
+
+def quantize_mx4(w: torch.Tensor):
+    """[N, K] float (K % 32 == 0) -> (codes uint8 [N, K] in 0..15, sb uint8 [N, K/32]).
+    Per 32-block the OCP MX rule: exponent floor(log2(absmax)) - 2, byte = exponent + 127
+    clamped to [2, 252] (127 for an all-zero block); w / 2^e clamped to +-6 and rounded to
+    the nearest e2m1 value, ties to the even code.  NaN / Inf raise."""
+    if w.dim() != 2 or w.shape[1] % MX4_BLOCK:
+        raise ValueError(f"quantize_mx4: needs [N, K] with K % 32 == 0, got {tuple(w.shape)}")
+    # fp64: exact on every backend, so a GPU and a CPU quantization agree bit for bit
+    wd = w.double()
+    if not bool(torch.isfinite(wd).all()):
+        raise ValueError("quantize_mx4: the weight holds NaN or Inf")
+    n, k = wd.shape
+    blk = wd.view(n, k // MX4_BLOCK, MX4_BLOCK)
+    amax = blk.abs().amax(-1)
+    _, ex = torch.frexp(amax)                    # amax = m 2^ex, m in [0.5, 1)
+    e = ex.to(torch.int64) - 1 - 2               # floor(log2(amax)) - 2
+    sb = torch.where(amax > 0, (e + 127).clamp(MX4_SB_MIN, MX4_SB_MAX), torch.full_like(e, 127))
+    scale = torch.ldexp(torch.ones_like(amax), (sb - 127).to(torch.int32))
+    a = (blk / scale.unsqueeze(-1)).clamp(-6.0, 6.0)
+    m = a.abs()
+    # midpoints of the grid; a tie goes to the even code of its two neighbours
+    mag = ((m > 0.25).to(torch.uint8) + (m >= 0.75).to(torch.uint8) + (m > 1.25).to(torch.uint8)
+           + (m >= 1.75).to(torch.uint8) + (m > 2.5).to(torch.uint8) + (m >= 3.5).to(torch.uint8)
+           + (m > 5.0).to(torch.uint8))
+    sign = ((a < 0) & (mag > 0)).to(torch.uint8) << 3
+    return (mag | sign).view(n, k).contiguous(), sb.to(torch.uint8).contiguous()
+
+
+def dequantize_mx4(codes: torch.Tensor, sb: torch.Tensor, dtype: torch.dtype = torch.float32):
+    """fp4(code) * 2^(sb - 127) per 32-block; exact in fp64, fp32 and (scale bytes in
+    [2, 252]) bf16."""
+    n, k = codes.shape
+    lut = torch.tensor(MX4_GRID + tuple(-v for v in MX4_GRID), dtype=torch.float64, device=codes.device)
+    v = lut[codes.long()].view(n, k // MX4_BLOCK, MX4_BLOCK)
+    e = sb.view(torch.uint8).to(torch.int32) - 127
+    s = torch.ldexp(torch.ones(e.shape, dtype=torch.float64, device=codes.device), e)
+    return (v * s.unsqueeze(-1)).view(n, k).to(dtype)
+
+
+def mx4_from_packed(wbytes: torch.Tensor, scales: torch.Tensor):
+    """Checkpoint layout (wbytes [N, K/2] uint8 / float4_e2m1fn_x2: two codes per byte, the
+    even k in the LOW nibble; scales [N, K/32] uint8 / float8_e8m0fnu) -> (codes, sb)."""
+    b = wbytes.view(torch.uint8)
+    codes = torch.stack([b & 0xF, b >> 4], dim=-1).reshape(b.shape[0], b.shape[1] * 2)
+    return codes.contiguous(), scales.view(torch.uint8).contiguous()
+
+
+def mx4_to_packed(codes: torch.Tensor, sb: torch.Tensor):
+    """Inverse of :func:`mx4_from_packed`: (wbytes uint8 [N, K/2], scales uint8 [N, K/32])."""
+    c = codes.view(codes.shape[0], -1, 2)
+    return (c[..., 0] | (c[..., 1] << 4)).contiguous(), sb.contiguous()
+
+
+def pack_mx4(codes: torch.Tensor, sb: torch.Tensor, gate_up: bool = False,
+             name: str = "scale bytes") -> MX4Weight:
+    """(codes, sb) -> the kernel image (csrc/kernels/mx4a16.hip documents it).
+    wq[tile][step][lane][16 B], lane = g * 16 + r: column 16 tile + r, k = 128 step + 32 g
+    + 0..31 (MX block 4 step + g, so ONE scale byte per 16-byte load); dword j holds k =
+    128 step + 32 g + 8 j + e in nibble e, the low nibble of byte e / 2 first, and is the
+    B fragment of the step's j-th 16x16x32 MFMA.  sc[tile][step][lane] is the lane's scale
+    byte.  ``gate_up``: rows (gate then up) and their scale rows are first interleaved in
+    16-row groups, the order the SiLU epilogues expect.  Scale bytes outside [2, 252]
+    raise, naming ``name``."""
+    n, k = codes.shape
+    if n % 16 or k % MX4_KSTEP:
+        raise ValueError(f"MX4 needs N % 16 == 0 and K % 128 == 0 (N = {n}, K = {k})")
+    if codes.dtype != torch.uint8 or sb.dtype != torch.uint8:
+        raise ValueError(f"pack_mx4: codes and scale bytes must be uint8, not {codes.dtype} / {sb.dtype}")
+    if tuple(sb.shape) != (n, k // MX4_BLOCK):
+        raise ValueError(f"pack_mx4: scale bytes {tuple(sb.shape)}, expected {(n, k // MX4_BLOCK)}")
+    if bool((codes > 15).any()):
+        raise ValueError("pack_mx4: codes must lie in 0..15")
+    if gate_up and n % 32:
+        raise ValueError(f"pack_mx4: a gate_up image needs N % 32 == 0 (N = {n})")
+    mx4_check_scale_bytes(sb, name)
+    if gate_up:
+        codes, sb = _interleave16(codes), _interleave16(sb)
+    b, _ = mx4_to_packed(codes, sb)              # [N, K/2], 64 bytes per k-step, 16 per g
+    # (tile, r, step, g, byte) -> (tile, step, g, r, byte)
+    wq = b.reshape(n // 16, 16, k // 128, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+    sc = sb.reshape(n // 16, 16, k // 128, 4).permute(0, 2, 3, 1).contiguous().view(-1)
+    return MX4Weight(wq, sc, n, k)
+
+
+def unpack_mx4(w: MX4Weight, gate_up: bool = False):
+    """Inverse of :func:`pack_mx4`: (codes uint8 [N, K], sb uint8 [N, K/32])."""
+    n, k = w.n, w.k
+    b = w.wq.view(n // 16, k // 128, 4, 16, 16).permute(0, 3, 1, 2, 4).contiguous().view(n, k // 2)
+    sb = w.sc.view(n // 16, k // 128, 4, 16).permute(0, 3, 1, 2).contiguous().view(n, k // 32)
+    codes, sb = mx4_from_packed(b, sb)
+    if gate_up:
+        codes, sb = _deinterleave16(codes), _deinterleave16(sb)
+    return codes.contiguous(), sb.contiguous()
+
+
+def _mx4_ref(x: torch.Tensor, w: MX4Weight) -> torch.Tensor:
+    """The contract in fp32 on the CPU: x dequant(W)^T, image row order."""
+    return x.float() @ dequantize_mx4(*unpack_mx4(w)).t()
+
+
+def _mx4_cpu_out(y: torch.Tensor, x, m: int, n: int, ws, splits: int, out, slab: bool, silu: bool):
+    if slab:   # the whole product in slab 0
+        slabs = ws.view(-1)[:splits * m * n].view(splits, m, n)
+        slabs.zero_()
+        slabs[0].copy_(y)
+        return ws
+    if silu:
+        g, u = y.view(m, -1, 2, 16).unbind(2)
+        y = (torch.nn.functional.silu(g) * u).reshape(m, -1)
+    y = y.to(x.dtype)
+    if out is not None:
+        out[:m, :y.shape[1]].copy_(y)
+        return out
+    return y
+
+
+def mx4_gemm(x: torch.Tensor, w: MX4Weight, out=None, ws=None, splits: int = 1, nt: int = 2,
+             silu: bool = False):
+    """y = x dequant(W)^T for M <= 64 rows (csrc/kernels/mx4a16.hip).  With ``ws`` the
+    kernel leaves fp32 slabs ([splits, M, N]) for a fused epilogue and returns ``ws``;
+    otherwise it returns bf16 ``out``.  ``nt``: 16-column tiles per wave (1, 2, 4).
+    ``silu``: h = silu(gate) * up of a ``pack_mx4(..., gate_up=True)`` image, [M, N / 2]
+    (nt 2, one split, no workspace)."""
+    m = x.shape[0]
+    if m > 64:
+        raise ValueError(f"mx4_gemm: M = {m} > 64 (use mx4_packed_gemm)")
+    if nt not in MX4_NTS:
+        raise ValueError(f"mx4_gemm: nt {nt} not in {MX4_NTS}")
+    if splits < 1 or w.k % (256 * splits):
+        raise ValueError(f"mx4_gemm: K {w.k} is not a multiple of 256 * splits ({splits})")
+    if silu and (ws is not None or splits != 1 or nt != 2 or w.n % 32):
+        raise ValueError("mx4_gemm: the SiLU epilogue is nt 2, one split, bf16 out, N % 32 == 0")
+    if splits > 1 and ws is None:
+        raise ValueError("mx4_gemm: splits > 1 needs a workspace")
+    if ws is not None and ws.numel() < splits * m * w.n:
+        raise ValueError(f"mx4_gemm: workspace too small ({ws.numel()} < {splits * m * w.n})")
+    if not x.is_cuda:
+        return _mx4_cpu_out(_mx4_ref(x, w), x, m, w.n, ws, splits, out, ws is not None, silu)
+    from . import native
+
+    if ws is None and out is None:
+        out = torch.empty(m, w.n // 2 if silu else w.n, dtype=x.dtype, device=x.device)
+    native().mx4_gemm(x, w.wq, w.sc, w.n, out, ws, splits, nt, silu)
+    return out if ws is None else ws
+
+
+def mx4_packed_gemm(x: torch.Tensor, w: MX4Weight, out=None, ws=None, splits: int = 1,
+                    epi: str = "store", cfg: int = 0):
+    """y = x dequant(W)^T for any row count on the same image
+    (csrc/kernels/mx4_packed_gemm.hip), with the decode kernel's numerics.  epi "store":
+    bf16 [M, N]; "slab": fp32 slabs [splits, M, N] in ``ws`` (any split count); "silu":
+    silu(gate) * up of a gate_up image -> [M, N / 2].  cfg 0 = the 128 x 256 tile.
+    Returns ``ws`` for slabs, else ``out``."""
+    code = _W4PG_EPI[epi]
+    m = x.shape[0]
+    if cfg != 0:
+        raise ValueError(f"mx4_packed_gemm: unknown tile shape cfg {cfg}")
+    if splits < 1 or w.k % (MX4_KSTEP * splits):
+        raise ValueError(f"mx4_packed_gemm: K {w.k} is not a multiple of 128 * splits ({splits})")
+    if code != 1 and splits != 1:
+        raise ValueError("mx4_packed_gemm: splits > 1 leaves slabs (epi='slab')")
+    if code == 2 and w.n % 32:
+        raise ValueError(f"mx4_packed_gemm: the SiLU epilogue needs N % 32 == 0 (N = {w.n})")
+    if code == 1 and ws is None:
+        raise ValueError("mx4_packed_gemm: slabs need a workspace")
+    if code == 1 and ws.numel() < splits * m * w.n:
+        raise ValueError(f"mx4_packed_gemm: workspace too small ({ws.numel()} < {splits * m * w.n})")
+    if not x.is_cuda:
+        return _mx4_cpu_out(_mx4_ref(x, w), x, m, w.n, ws, splits, out, code == 1, code == 2)
+    from . import native
+
+    if code != 1 and out is None:
+        out = torch.empty(m, w.n // 2 if code == 2 else w.n, dtype=x.dtype, device=x.device)
+    native().mx4_packed_gemm(x, w.wq, w.sc, w.n, out, ws, splits, code, cfg)
     return ws if code == 1 else out
